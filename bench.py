@@ -17,9 +17,16 @@ N > 1 runs N independent TP=1 replicas, one process per GPU: started under torch
 --gpus N` spawns its own N ranks through torch.distributed.run before touching a GPU and exits with
 their code (the reference's server spawns one process per rank the same way, server/server.py:252-265).
 There is no data-path collective: ranks only meet at the timing barriers.
-Rank 0 prints ONE JSON line.  After the decode measurement the same engine runs config 3 (64 prompts,
-lengths U[128,4096]) once warm and once timed: ttft_p50_ms / ttft_p99_ms / prefill_tokens_per_sec and a
-`roofline_prefill` block (extend attention kernel vs the dense bf16 MFMA peak) are part of the line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line (metric,
+value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step, and figures computed from
+them).  `--full` adds what takes runs of its own: the dominant kernel's HBM roofline (extra eager steps with HIP
+events), config 3 on the same engine (64 prompts, lengths U[128,4096]) once warm and once timed
+(ttft_p50_ms / ttft_p99_ms / prefill_tokens_per_sec and a `roofline_prefill` block: extend attention kernel vs
+the dense bf16 MFMA peak), the CPU baselines and, with N > 1, an RCCL all-reduce over the replicas.
+
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+writes what the last timed step handed back (next token ids, and the logits at a fixed seeded sample of the
+vocabulary columns) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared file by file.
 
   python bench.py --mode tp --gpus 8 --tp 8 --model llama3-70b          (config 4)
 runs the REAL sharded model (heads, KV pool, linears per rank; RCCL all-reduce after o_proj / down_proj
@@ -48,8 +55,13 @@ MFMA_PEAK_TFLOPS = 2500.0  # dense bf16/fp16 MFMA peak (MI355X_MICROARCH.md: ~2.
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=64)
-    ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 64; prefill mode 3, tp mode 32)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 8; prefill 1, tp 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="decode mode: also the attention roofline, the config-3 TTFT passes, the CPU baselines and the "
+                         "RCCL check of the replicas (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="decode mode: write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--bs", type=int, default=256)
     ap.add_argument("--ctx", default="uniform", help='"uniform" = U[128,4096] seed 0, or a fixed length')
     ap.add_argument("--model", default=None,
@@ -83,6 +95,13 @@ def parse_args():
     ap.add_argument("--profile-steps", type=int, default=4,
                     help="extra eager steps with HIP events around every attention launch")
     args = ap.parse_args()
+    steps, warmup = {"prefill": (3, 1), "tp": (32, 4)}.get(args.mode, (64, 8))
+    args.steps = steps if args.steps is None else args.steps
+    args.warmup = warmup if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode != "decode":
+        ap.error("--dump-outputs is implemented for the decode mode (the headline workload) only")
     if args.model is None:
         args.model = "llama3-70b" if args.mode == "tp" else "llama3-8b"
     if args.mode == "tp" and args.bs == 256:
@@ -177,17 +196,19 @@ def build_engine(args, device_index, seed, tp_rank=0, tp_size=1):
                        cuda_graph_bs=[args.bs], kv_cache_dtype=args.kv_cache_dtype)
     mr = ModelRunner(cfg, sargs, tp_rank=tp_rank, tp_size=tp_size, dtype=torch.bfloat16, gpu_id=device_index,
                      seed=seed)
-    # synthetic cache contents (random, not zeros: zero operands run at a higher clock)
+    # synthetic cache contents (random, not zeros: zero operands run at a higher clock), from a generator seeded
+    # here: the process-wide default one is not, and the outputs of a run must repeat from one run to the next
+    kv_gen = torch.Generator(device=mr.device).manual_seed(seed)
     for arena in (mr.token_to_kv_pool._k_arena, mr.token_to_kv_pool._v_arena):
         for layer in range(arena.shape[0]):
             if arena.dtype == torch.uint8:      # e5m2 bytes of the same distribution
                 rows = arena[layer]
                 for lo in range(0, rows.shape[0], 1 << 17):
                     blk = rows[lo:lo + (1 << 17)]
-                    blk.copy_(torch.empty(blk.shape, dtype=torch.bfloat16, device=blk.device).normal_(0.0, 0.5)
-                              .to(torch.float8_e5m2).view(torch.uint8))
+                    blk.copy_(torch.empty(blk.shape, dtype=torch.bfloat16, device=blk.device)
+                              .normal_(0.0, 0.5, generator=kv_gen).to(torch.float8_e5m2).view(torch.uint8))
             else:
-                arena[layer].normal_(0.0, 0.5)
+                arena[layer].normal_(0.0, 0.5, generator=kv_gen)
     return mr, ctx, gen
 
 
@@ -226,6 +247,23 @@ def engine_step(worker, batch):
     out, next_ids = worker.forward_batch_generation(batch.get_model_worker_batch())
     batch.output_ids = next_ids
     return out
+
+
+def dump_outputs(path, logits_output, next_ids, max_columns=8192):
+    """What a caller of the decode step receives, as DIR/<name>.npy: the next token ids (float64, exact) and the
+    fp32 logits [bs, vocab] at a fixed, seeded sample of the vocabulary columns (the whole matrix is 131 MB at bs
+    256), with the sampled column indices.  At most 48 MB of logits whatever the batch size."""
+    import numpy as np
+    logits = logits_output.gather_full_logits()
+    bs, vocab = logits.shape
+    n = max(1, min(vocab, max_columns, (48 << 20) // (4 * bs)))
+    cols = torch.randperm(vocab, generator=torch.Generator().manual_seed(0))[:n].sort().values
+    os.makedirs(path, exist_ok=True)
+    arrays = {"next_token_ids": next_ids.detach().cpu().to(torch.float64),
+              "next_token_logits_sample": logits[:, cols.to(logits.device)].cpu(),
+              "next_token_logits_sample_columns": cols.to(torch.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
 
 
 def attention_algorithmic_bytes(cfg, seq_sum, bs, kv_elem=2):
@@ -897,8 +935,6 @@ def main():
     from scratchpad_amd.model_runner import TpModelWorker
     _native.load()
     if args.mode == "tp":
-        if args.steps == 64:
-            args.steps, args.warmup = 32, 4
         tp_main(args, rank, local_rank, world)
         return
     if world > 1:
@@ -911,8 +947,6 @@ def main():
     if shared and not args.rehearsal:      # (pick_device already refuses on one host; this covers odd launchers)
         raise SystemExit(f"{world} ranks on {devices_seen(seen)} device(s): refusing without --rehearsal")
     if args.mode == "prefill":
-        if args.steps == 64:
-            args.steps, args.warmup = 3, 1
         prefill_main(args, rank, local_rank, world)
         return
     if args.mode == "serve":
@@ -929,11 +963,13 @@ def main():
     batch = populate_batch(mr, ctx, gen)
 
     def run_steps(n):
-        """n decode steps; with --overlap the scheduler side runs one step ahead of the results"""
+        """n decode steps; with --overlap the scheduler side runs one step ahead of the results.
+        Returns what the last step handed back: (logits output, next token ids), or None for n = 0."""
         if overlap_worker is None:
+            out = None
             for _ in range(n):
-                engine_step(worker, batch)
-            return
+                out = engine_step(worker, batch)
+            return None if out is None else (out, batch.output_ids)
         pending = 0
         for _ in range(n):
             batch.prepare_for_decode()
@@ -943,7 +979,9 @@ def main():
                 overlap_worker.resolve_last_batch_result()
             pending = 1
         if pending:
-            overlap_worker.resolve_last_batch_result()
+            out, ids = overlap_worker.resolve_last_batch_result()
+            return out, torch.tensor(ids, dtype=torch.int64)
+        return None
 
     def barrier():
         torch.cuda.synchronize()
@@ -955,7 +993,7 @@ def main():
     barrier()
     seq_sum_start = batch.seq_lens_sum
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last = run_steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
     seq_sum_end = batch.seq_lens_sum
@@ -963,6 +1001,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:     # before anything else runs on the engine (graph outputs are reused buffers)
+        dump_outputs(args.dump_outputs, *last)
 
     # ---- dominant kernel: paged decode attention, timed per launch with HIP events on the
     # stream it is launched on (eager steps continuing the same trace)
@@ -970,7 +1010,7 @@ def main():
     roofline = None
     if overlap_worker is not None:
         overlap_worker.close()
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         saved = mr.graph_runner
         mr.graph_runner = None
         events, sums, calls = [], [], []
@@ -1031,7 +1071,7 @@ def main():
     # U[128,4096], extend batches <= max_prefill_tokens): one warm pass, one timed pass, one pass with
     # HIP events around the extend-attention launches (every rank runs them; rank 0 reports its own)
     ttft = None
-    if not args.no_ttft and args.model == "llama3-8b" and cfg.context_len >= 4100:
+    if args.full and not args.no_ttft and args.model == "llama3-8b" and cfg.context_len >= 4100:
         el_p, tt_p, lens_p, nb_p, prof_p = prefill_passes(args, mr, worker, rank, 64, 1, 1, profile_attention=rank == 0)
         ttft = {"ttft_p50_ms": round(tt_p[len(tt_p) // 2] * 1e3, 2), "ttft_p99_ms": round(tt_p[int(len(tt_p) * 0.99)] * 1e3, 2),
                 "prefill_tokens_per_sec": round(sum(lens_p) / el_p, 1),
@@ -1040,7 +1080,7 @@ def main():
                                    "prompt_tokens": sum(lens_p), "extend_batches": nb_p, "pass_ms": round(el_p * 1e3, 1)},
                 "roofline_prefill": prefill_roofline(prof_p)}
         barrier()
-    rccl_ranks, rccl_note = rccl_sanity(world, local_rank, shared)
+    rccl_ranks, rccl_note = rccl_sanity(world, local_rank, shared) if args.full else (None, "not run: --full only")
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
@@ -1081,7 +1121,7 @@ def main():
         out.update(ttft)
     if roofline is not None:
         out["roofline"] = roofline
-    if not args.no_cpu_baseline and world == 1:     # the CPU legs are timed on rank 0 of the 1-GPU run only
+    if args.full and not args.no_cpu_baseline and world == 1:     # the CPU legs: rank 0 of the 1-GPU run only
         out["cpu_baseline"] = cpu_baseline()
         out["cpu_baseline_cfg1"] = cpu_baseline_cfg1()
     print(json.dumps(out), flush=True)

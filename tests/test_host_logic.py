@@ -146,7 +146,8 @@ def test_rope_cache_is_the_references_bit_for_bit():
         sc = golden.rope_scaling(g, i)          # None, llama3, or (round 4) linear / dynamic NTK / YaRN
         rope = get_rope(int(g[f"c{i}_head_size"]), int(g[f"c{i}_rotary_dim"]), int(g[f"c{i}_max_pos"]),
                         float(g[f"c{i}_base"]), bool(g[f"c{i}_neox"]), sc, dtype=torch.float32)
-        assert np.array_equal(rope.cos_sin_cache.numpy(), g[f"c{i}_cos_sin_cache"]), f"case {i} {sc}"
+        # (get_rope's cache is process-wide: a GPU test earlier in the session may have moved this module to the GPU)
+        assert np.array_equal(rope.cos_sin_cache.cpu().numpy(), g[f"c{i}_cos_sin_cache"]), f"case {i} {sc}"
     a = get_rope(64, 64, 128, 10000, True, None, torch.float32)
     assert a is get_rope(64, 64, 128, 10000, True, None, torch.float32), "cached per key"
     assert get_rope(64, 64, 128, 10000, True, None, torch.float32, partial_rotary_factor=0.5).rotary_dim == 32

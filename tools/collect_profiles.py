@@ -19,7 +19,7 @@ def main(tag):
     ks = open(os.path.join(R, "kernel_stats.txt")).read().rstrip().split("\n")
     b = last_json(os.path.join(R, "prof_bench.json"))
     hdr = (f"# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 16 --warmup 4 "
-           f"--no-cpu-baseline --no-ttft   (MI355X; tools/gpu_round_report.sh)\n"
+           f"--full --no-cpu-baseline --no-ttft   (MI355X; tools/gpu_round_report.sh)\n"
            f"# bench line of this run: {b['value']} tokens/s, {b['ms_per_step']} ms/step; roofline: "
            f"{json.dumps(b['roofline'])}\n"
            f"# decode_mfma_* rows include 2x32 graph-capture warm-up launches at the padded fill length (min_us).\n")

@@ -89,7 +89,7 @@ for N in 1 2 4 8; do
   fits $N || { SUMMARY+=("02_replicas_$N: skipped (needs $N devices)"); continue; }
   EXTRA=""
   [ $REHEARSAL -eq 1 ] && EXTRA="--layers 4 --steps 4 --warmup 1 --no-cpu-baseline --no-ttft"
-  run 02_replicas_$N 900 python bench.py --gpus $N $RH $EXTRA && line 02_replicas_$N
+  run 02_replicas_$N 900 python bench.py --gpus $N --full $RH $EXTRA && line 02_replicas_$N
 done
 
 # ---- step 3: config 4, Llama-3-70B sharded TP = 8 (8 q heads + 1 kv head per rank), bs 128, RCCL all-reduce, eager and

@@ -5,15 +5,16 @@
 # bench.py:pmc_traffic prefers this in-model record (same kernel-source hash, same workload key) over the kernel-alone one.
 #   bash tools/pmc_bench.sh [KEY] [bench.py arguments ...]
 set -o pipefail
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 KEY=${1:-"llama3-8b|bs256|ctxuniform|kvauto"}; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_bench
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="$GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-ttft --profile-steps 1 $*"
+B="$ROOT/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-ttft --profile-steps 1 $*"
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/f -- python3 $B > $OUT/f.log 2>&1 &&
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/w -- python3 $B > $OUT/w.log 2>&1 || { tail -5 $OUT/f.log $OUT/w.log; exit 1; }
 cd $GRAFT_REPO_ROOT
-{ echo "# rocprofv3 --pmc {FETCH_SIZE | WRITE_SIZE} --kernel-trace -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-ttft --profile-steps 1 $*"
+{ echo "# rocprofv3 --pmc {FETCH_SIZE | WRITE_SIZE} --kernel-trace -- python3 bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-ttft --profile-steps 1 $*"
   python tools/pmc_summary.py $OUT/f decode_mfma_ decode_merge_kernel
   python tools/pmc_summary.py $OUT/w decode_mfma_ decode_merge_kernel
   grep -h '^{"metric"' $OUT/f.log | tail -1 | cut -c1-600; } > $OUT/summary.txt
