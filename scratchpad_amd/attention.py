@@ -156,7 +156,10 @@ class HipAttnBackend(AttentionBackend):
         # The (request, split) items are planned only where a launch of this model can read them (round 6; the reference's
         # init_forward_metadata computes only what its one kernel reads, triton_backend.py:48-68): a shape the range kernel
         # refuses, or a layer with a logit soft-cap (Gemma-2 style; no Llama-3 / Mllama layer has one).  Without them a
-        # plan is the range section alone and nothing of a step depends on the host's bound on sum(seq_lens).
+        # plan is the range section alone and nothing of a step depends on the host's bound on sum(seq_lens): the range
+        # section is cut from the device-side lengths, and the bound they are clamped to (max_len) comes from the host's
+        # copy of the lengths or from the context length, never from the sum (init_forward_metadata).  With them the sum
+        # sizes the items' slots, and _watch_plan reports a step whose lengths needed more.
         layers = [m for m in getattr(model_runner, "model", nn.Module()).modules() if isinstance(m, RadixAttention)]
         self.plan_items = self.decode_ranges <= 0 or any(m.logit_cap > 0 for m in layers)
 
@@ -303,14 +306,20 @@ class HipAttnBackend(AttentionBackend):
         max_seq_len, workspace).  No device sync: bounds come from host-side fields."""
         pool_dtype = forward_batch.token_to_kv_pool.dtype
         bs = forward_batch.batch_size
+        # max_len is the bound every kernel clamps each length to, so it may never fall below the longest one.  Without
+        # host copies of the lengths it is the context length - the width of the request table, which holds the encoder
+        # slots and the text behind them - as under graph replay (cuda_graph_max_seq_len).  The host's seq_lens_sum is
+        # no bound on the longest request: an understated sum would silently cut attention short.
         enc_max = 0
         if forward_batch.encoder_lens_cpu:
             enc_max = max(forward_batch.encoder_lens_cpu)
+        elif self.is_encoder_decoder and forward_batch.encoder_lens is not None:
+            enc_max = self.max_context_len
         if forward_batch.forward_mode.is_decode():
             if forward_batch.seq_lens_cpu is not None:
                 max_len = int(forward_batch.seq_lens_cpu.max())
             else:
-                max_len = min(self.max_context_len, forward_batch.seq_lens_sum - (bs - 1))
+                max_len = self.max_context_len
             max_len = max(max_len, enc_max, 1)
             enc = forward_batch.encoder_lens if self.is_encoder_decoder else None
             enc_sum = sum(forward_batch.encoder_lens_cpu) if forward_batch.encoder_lens_cpu else None

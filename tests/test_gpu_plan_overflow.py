@@ -135,9 +135,10 @@ def test_range_plans_do_not_size_anything_from_the_hosts_sum():
     """The backend as it is built for Llama / Mllama since round 6: plans carry the range section alone, whose slots
     (batch size + pieces) and cuts come from the device-side lengths.  A seq_lens_sum understated so far that the item
     geometry would drop splits (2000 claimed for 4 x 600: 35 slots for 40 items - the report of the tests above) changes
-    NOTHING here: the same bits as the honest step, nothing to report, no header copy per step.  (What the host's sum
-    still bounds in an eager step is the longest request, max_len = min(context, sum - (bs - 1)): lengths are clamped to
-    it, as on every path; 1997 >= 600 here.)"""
+    NOTHING here: the same bits as the honest step, nothing to report, no header copy per step.  Nor does a sum below the
+    longest request (400 claimed for 4 x 600): the bound every length is clamped to (max_len) is the context length in an
+    eager step without seq_lens_cpu, as under graph replay - it was min(context, sum - (bs - 1)) = 397 until the clamp
+    silently cut every request to 397 keys."""
     from scratchpad_amd import _native
     from scratchpad_amd.model_runner import TpModelWorker
     mr = _runner(items=False)
@@ -148,7 +149,83 @@ def test_range_plans_do_not_size_anything_from_the_hosts_sum():
     honest = honest.next_token_logits.clone()
     assert _native.decode_plan_slots(4, 1997, 64, 2000) < 4 * 10, "the item geometry would have overflowed"
     mr.attn_backend.strict_plan_check = True
-    bad, _ = worker.forward_batch_generation(_decode_batch(mr, lens, 2000))
-    assert torch.equal(bad.next_token_logits, honest)
-    assert not mr.attn_backend._plan_checks, "no item section: nothing is watched"
+    for claimed in (2000, 400):
+        bad, _ = worker.forward_batch_generation(_decode_batch(mr, lens, claimed))
+        assert _native.debug_get("decode_last_kernel") == 3
+        assert mr.attn_backend.forward_metadata[1] >= max(lens), f"claimed {claimed}: max_len below the longest request"
+        assert torch.equal(bad.next_token_logits, honest), f"claimed {claimed}: other logits than the honest step"
+        assert not mr.attn_backend._plan_checks, "no item section: nothing is watched"
+        mr.attn_backend.check_plans()
+
+
+def test_item_geometry_never_returns_a_cut_request_silently(item_geometry):
+    """lens [1000, 1, 1, 1] claimed as 500 in the (request, split) item geometry.  While max_len was derived from the
+    sum (min(context, 500 - 3) = 497) the plan counted its items from the CLAMPED lengths - 8 + 3 = 11, exactly the 11
+    slots 500 // 64 + 4 sizes - so nothing overflowed, nothing was reported and request 0 attended to 497 of its 1000
+    keys.  The step must give the honest logits or raise; it may never return other logits."""
+    from scratchpad_amd.model_runner import TpModelWorker
+    mr = _runner()
+    worker = TpModelWorker(mr)
+    lens = [1000, 1, 1, 1]
+    honest, _ = worker.forward_batch_generation(_decode_batch(mr, lens, sum(lens)))
+    honest = honest.next_token_logits.clone()
     mr.attn_backend.check_plans()
+    mr.attn_backend.strict_plan_check = True
+    try:
+        bad, _ = worker.forward_batch_generation(_decode_batch(mr, lens, 500))
+    except RuntimeError as e:
+        assert "split plan overflow" in str(e), e
+    else:
+        assert torch.equal(bad.next_token_logits, honest), "a cut request returned other logits, unreported"
+    # the engine goes on: the honest step again, the same bits
+    again, _ = worker.forward_batch_generation(_decode_batch(mr, lens, sum(lens)))
+    assert torch.equal(again.next_token_logits, honest)
+
+
+def test_cross_attention_window_without_encoder_lens_cpu():
+    """An encoder-decoder decode step whose ForwardBatch carries encoder_lens but not encoder_lens_cpu: the cross
+    window (up to 200 encoder keys here, behind text of <= 9 tokens) must not be clamped to the text's bound.  Checked
+    at the backend seam, layer by layer (the Mllama model itself reads encoder_lens_cpu for its row mask): the cross and
+    the self launch give the bits of the step that has the host copy, with and without seq_lens_cpu; a text-only request
+    (encoder_len 0) reads as zeros."""
+    from scratchpad_amd.attention import RadixAttention
+    from scratchpad_amd.forward_info import ForwardBatch, ForwardMode
+    from scratchpad_amd.model_runner import ModelConfig, ModelRunner, ServerArgs
+    cfg = ModelConfig(256, 512, 2, 4, 2, 512, context_len=256, max_position_embeddings=512, cross_attention_layers=[1])
+    mr = ModelRunner(cfg, ServerArgs(max_total_tokens=1024, max_running_requests=4, disable_cuda_graph=True),
+                     dtype=torch.bfloat16, seed=5)
+    be = mr.attn_backend
+    assert be.is_encoder_decoder and be.decode_ranges > 0 and be.plan_items is False
+    dev = mr.device
+    g = torch.Generator(device=dev).manual_seed(7)
+    for arena in (mr.token_to_kv_pool._k_arena, mr.token_to_kv_pool._v_arena):
+        arena.normal_(0.0, 1.0, generator=g)
+    enc, text = [200, 0, 150], [5, 9, 3]
+    table = mr.req_to_token_pool.req_to_token
+    perm = (torch.randperm(1000, generator=torch.Generator().manual_seed(8)) + 1).to(torch.int32).to(dev)
+    off = 0
+    for b, (e, t) in enumerate(zip(enc, text)):
+        table[b, :e + t] = perm[off:off + e + t]
+        off += e + t
+    cross = next(m for m in mr.model.modules() if isinstance(m, RadixAttention) and m.is_cross_attention)
+    selfa = next(m for m in mr.model.modules() if isinstance(m, RadixAttention) and not m.is_cross_attention)
+    q = torch.randn(3, 4 * 64, device=dev, generator=g).to(torch.bfloat16)
+
+    def step(enc_cpu, seq_cpu):
+        fb = ForwardBatch(forward_mode=ForwardMode.DECODE, batch_size=3, input_ids=torch.zeros(3, dtype=torch.int64, device=dev),
+                          req_pool_indices=torch.arange(3, device=dev), seq_lens=torch.tensor(text, device=dev),
+                          out_cache_loc=torch.zeros(3, dtype=torch.int64, device=dev), seq_lens_sum=sum(text),
+                          seq_lens_cpu=torch.tensor(text) if seq_cpu else None,
+                          encoder_lens=torch.tensor(enc, device=dev), encoder_lens_cpu=list(enc) if enc_cpu else None,
+                          req_to_token_pool=mr.req_to_token_pool, token_to_kv_pool=mr.token_to_kv_pool, attn_backend=be)
+        be.init_forward_metadata(fb)
+        assert be.forward_metadata[1] >= max(enc), "max_len below the longest encoder window"
+        return [be.forward_decode(q.clone(), None, None, layer, fb, save_kv_cache=False).clone() for layer in (cross, selfa)]
+
+    honest = step(True, True)
+    assert torch.all(honest[0][1] == 0), "a text-only request's cross-attention row reads as zeros"
+    assert not torch.equal(honest[0][0], honest[0][2])
+    for seq_cpu in (True, False):
+        got = step(False, seq_cpu)
+        for what, a, b in zip(("cross", "self"), got, honest):
+            assert torch.equal(a, b), f"{what} launch without encoder_lens_cpu (seq_lens_cpu: {seq_cpu}): other bits"
