@@ -642,6 +642,9 @@ extern "C" int sp_decode_plan(int32_t* plan, size_t plan_bytes, const void* seq_
   SP_CHECK_ARG(max_slots > 0 || ranges > 0);           // (a plan with neither section plans nothing)
   SP_CHECK_ARG(ranges == 0 || range_line_fits(batch_size, max_seq_len));
   if (plan_bytes < sp_decode_plan_bytes(batch_size, max_slots, ranges)) return SP_ERR_WORKSPACE;
+  // an empty batch: sp_decode_plan_bytes() sized no sections (16 bytes) and the launches of the step return at once
+  // without reading the plan - writing the sections here would run past the caller's buffer
+  if (batch_size == 0) return SP_OK;
   decode_plan_kernel<<<dim3(1), 256, 0, (hipStream_t)stream>>>(plan, seq_lens, idx64, batch_size,
                                                                chunk, (int)max_seq_len, (int)max_slots, ranges);
   SP_LAUNCH_CHECK();

@@ -129,6 +129,9 @@ extern "C" int sp_extend_plan(int32_t* plan, size_t plan_bytes, const int32_t* e
   SP_CHECK_ARG(plan && extend_seq_lens && seq_lens && batch_size >= 0 && num_tokens >= 0);
   SP_CHECK_ARG(num_q_heads > 0 && num_kv_heads > 0 && num_q_heads % num_kv_heads == 0);
   if (plan_bytes < sp_extend_plan_bytes(num_tokens, batch_size, num_q_heads, num_kv_heads)) return SP_ERR_WORKSPACE;
+  // an empty step: sp_extend_plan_bytes() sized 16 bytes, no header, items or counters, and sp_extend_attention returns at
+  // once without reading the plan - writing them here would run past the caller's buffer
+  if (batch_size == 0 || num_tokens == 0) return SP_OK;
   const int bm = extend_block_rows(num_q_heads, num_kv_heads);
   const int64_t items = extend_plan_items(num_tokens, batch_size, bm);
   if (items > 0x3fffffffLL || num_tokens > 0x7fffffffLL) return SP_ERR_INVALID_ARG;
