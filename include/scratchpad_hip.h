@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 9
+#define SP_ABI_VERSION 10   /* v10: `chunk` is the smallest split size a plan carries; plan word 2 never exceeds word 0 */
 #define SP_API __attribute__((visibility("default")))
 
 typedef enum { SP_F32 = 0, SP_F16 = 1, SP_BF16 = 2, SP_FP8_E5M2 = 3 /* KV pool only */ } sp_dtype;
@@ -177,8 +177,7 @@ SP_API int sp_clamp_position(int64_t* positions, const void* seq_lens, int idx64
  * wave gathers the same number of keys whatever the lengths are, there is no split size to choose, and a request is
  * written straight to the output unless a cut falls inside it.  A request whose keys lie in pieces jf .. jl > jf leaves
  * its partials in slots b + jf .. b + jl (b + j grows along the line: no two (request, piece) pairs share a slot) and
- * the merge launch combines them: the workspace then holds batch_size + ranges slots, whatever sum(seq_lens) is - the
- * overflow below cannot happen on this path.
+ * the merge launch combines them: the workspace then holds batch_size + ranges slots, whatever sum(seq_lens) is.
  * sp_decode_ranges() is the piece count the library wants for a shape ON THE CURRENT DEVICE (the answer, and the
  * kernel's LDS limit behind it, are kept per device of the process: set the device before the first call, as for any
  * launch): two workgroups per CU (three on a byte pool), all resident at once, four waves each, over the kv heads (at
@@ -205,10 +204,12 @@ SP_API int sp_clamp_position(int64_t* positions, const void* seq_lens, int idx64
  *     SP_ERR_INVALID_ARG.  Likewise ranges = 0 builds the items alone.  sp_debug_get("decode_last_kernel") says what the
  *     last call launched: 1 = VALU kernel (items), 2 = matrix-core kernel (items), 3 = range kernel.
  *
- * Overflow (ABI 6).  The plan's word 2 holds the number of items the lengths NEED; when it exceeds `max_slots`
- * (the caller's bound on sum(seq_lens) was too small) the surplus splits are not computed and the affected
- * output rows are wrong or unwritten.  Nothing on the device reports this by itself: the caller reads plan[2]
- * (a 16-byte copy of the header at a point where it synchronises anyway) and raises - HipAttnBackend does.
+ * Every item fits (ABI 10).  sp_decode_plan lists every split of the (clamped) device-side lengths: where they need
+ * more than `max_slots` items at `chunk` (the caller's bound on sum(seq_lens) was too small) the plan kernel doubles the
+ * split size until they fit, and word 1 carries the size it chose.  At a split size >= max_seq_len every non-empty
+ * request is one item, so an item plan requires max_slots >= batch_size and max_seq_len <= 2^30 (else
+ * SP_ERR_INVALID_ARG).  An understated bound costs load balance, never a split; word 2 (the items the lengths need)
+ * equals word 0 (the items listed).
  *
  * Streaming gathers.  The plan's word 3 holds the keys the step gathers per kv head (the sum of the clamped lengths).
  * When a launch's K + V bytes (that sum x 2 x num_kv_heads x head_dim x element size) reach a threshold

@@ -122,7 +122,7 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.sp_abi_version() != 9:
+    if lib.sp_abi_version() != 10:
         raise RuntimeError("libscratchpad_hip.so ABI version mismatch")
     _lib = lib
     return lib
@@ -382,9 +382,6 @@ def decode_ranges(Hq: int, Hkv: int, D: int, dtype: torch.dtype, kv_dtype: Optio
     return int(load().sp_decode_ranges(Hq, Hkv, D, dt, kv))
 
 
-PLAN_HEADER_WORDS = 4          # [items listed, chunk, items the lengths need, keys the step gathers per kv head]
-
-
 def _plan_slots(bs: int, max_seq_len: int, chunk: int, max_slots: Optional[int]) -> int:
     return decode_plan_slots(bs, max_seq_len, chunk) if max_slots is None else int(max_slots)
 
@@ -418,8 +415,9 @@ def decode_plan(plan: torch.Tensor, seq_lens: torch.Tensor, max_seq_len: int, ch
                 max_slots: Optional[int] = None, ranges: int = 0) -> None:
     """Fill `plan` (int32: [count, chunk, needed, keys | slot0[bs] | (request, split) x max_slots]) for this
     step's lengths.  `max_slots`: the item / partial-slot capacity the launches using this plan are given (default:
-    the static bound bs * ceil(max_seq_len / chunk); 0 with ranges > 0: no items, the plan serves range launches only).
-    plan[2] > max_slots afterwards means the capacity was too small (see decode_plan_overflow).
+    the static bound bs * ceil(max_seq_len / chunk); 0 with ranges > 0: no items, the plan serves range launches only;
+    else at least bs).  Where the lengths need more items than that at `chunk`, the plan carries a larger split size
+    (plan[1], ABI 10) and still lists every item.
     `ranges` > 0 appends the range geometry ([pieces, R, ranges, bs | pos[bs + 1] | start[ranges]],
     include/scratchpad_hip.h) for launches given the same `ranges`."""
     _gpu(plan, seq_lens)
@@ -436,17 +434,6 @@ def decode_plan(plan: torch.Tensor, seq_lens: torch.Tensor, max_seq_len: int, ch
     if len(_BUILT_PLANS) >= _BUILT_PLANS_MAX:
         del _BUILT_PLANS[next(iter(_BUILT_PLANS))]
     _BUILT_PLANS[key] = (weakref.ref(plan), (bs, max_slots, int(ranges)))
-
-
-def decode_plan_overflow(header, max_slots: int) -> Optional[str]:
-    """`header`: the first PLAN_HEADER_WORDS ints of a plan, on the host.  None if the plan lists every split the
-    lengths need; otherwise the error text (splits were dropped: outputs of this step are wrong)."""
-    listed, chunk, needed = int(header[0]), int(header[1]), int(header[2])
-    if needed <= max_slots:
-        return None
-    return (f"decode split plan overflow: the step's seq_lens need {needed} (request, split) items at split size "
-            f"{chunk} but the launch was sized for {max_slots} (listed {listed}): the bound on sum(seq_lens) handed to "
-            "the attention backend (ForwardBatch.seq_lens_sum) is smaller than the lengths on the device")
 
 
 def decode_attention(out: torch.Tensor, q: torch.Tensor, k_buffer: torch.Tensor,

@@ -8,7 +8,6 @@ implements the flashinfer backend's encoder-decoder dispatch (cross-attention re
 [0, encoder_len); self-attention reads [encoder_len, encoder_len + seq_len)).
 """
 import os
-import threading
 from abc import ABC, abstractmethod
 from typing import TYPE_CHECKING, Optional
 
@@ -113,10 +112,7 @@ class HipAttnBackend(AttentionBackend):
     # graph replay: a captured launch of bucket bs covers max(FLOOR, PER_REQ x bs) + bs work items / partial slots
     GRAPH_SLOTS_FLOOR, GRAPH_SLOTS_PER_REQ = 1024, 8
     fused_rope_kv_store = True      # rotary + KV store as one kernel; False keeps the reference's two-step order
-    # True: every plan's overflow word is read back right after it is built (one device sync per step: tests,
-    # debugging).  False: the 16-byte header is copied to pinned memory asynchronously and checked when the
-    # NEXT plan is built, or by check_plans() - an understated seq_lens_sum raises one step late instead of never
-    strict_plan_check = False
+    _graph_ranges = None            # range pieces of every captured launch: set by init_cuda_graph_state
 
     def __init__(self, model_runner):
         super().__init__()
@@ -143,10 +139,6 @@ class HipAttnBackend(AttentionBackend):
         self._graph_ws = None          # graph replay: ONE partials workspace / plan-buffer triple for all buckets
         self._graph_plans = None
         self._extend_plan = None       # int32 work list of the current extend step (sp_extend_plan)
-        self._plan_checks = []         # (pinned header copy, event, max_slots, step) of item plans not yet checked
-        self.plan_step = None          # the overlap worker's step number while its forward thread builds that step's plans
-        self._plan_hosts = []          # pinned buffers + events to reuse
-        self._plan_lock = threading.Lock()   # the overlap worker checks from the scheduler thread (tp_worker_client.py)
         # Range geometry (include/scratchpad_hip.h): the pieces the step's keys are cut into, one wave per (piece, kv head),
         # two workgroups per CU; 0 where the range kernel does not take the shape (fp32, groups wider than 16).
         # SP_DECODE_RANGES=0 switches it off, =N forces N pieces (A/B runs).
@@ -159,7 +151,8 @@ class HipAttnBackend(AttentionBackend):
         # plan is the range section alone and nothing of a step depends on the host's bound on sum(seq_lens): the range
         # section is cut from the device-side lengths, and the bound they are clamped to (max_len) comes from the host's
         # copy of the lengths or from the context length, never from the sum (init_forward_metadata).  With them the sum
-        # sizes the items' slots, and _watch_plan reports a step whose lengths needed more.
+        # sizes the items' slots and their split size; lengths that need more items get a larger split from the plan
+        # kernel (ABI 10), so an understated sum costs balance, not correctness.
         layers = [m for m in getattr(model_runner, "model", nn.Module()).modules() if isinstance(m, RadixAttention)]
         self.plan_items = self.decode_ranges <= 0 or any(m.logit_cap > 0 for m in layers)
 
@@ -187,14 +180,17 @@ class HipAttnBackend(AttentionBackend):
         return self._workspace
 
     def _graph_slots(self, bs: int) -> int:
-        """(request, split) items a captured launch of bucket `bs` covers; 0 where no launch of this model reads items"""
-        if not (self.plan_items or self._ranges_for(bs, self.max_context_len) <= 0):
+        """(request, split) items a captured launch of bucket `bs` covers; 0 where no launch of this model reads items.
+        Every bucket's launches take the range pieces decided for the largest one (init_cuda_graph_state)."""
+        ranges = self._graph_ranges if self._graph_ranges is not None else self._ranges_for(bs, self.max_context_len)
+        if not (self.plan_items or ranges <= 0):
             return 0
         by_len = bs * -(-self.max_context_len // self.MIN_CHUNK)
         return min(by_len, max(self.GRAPH_SLOTS_FLOOR, self.GRAPH_SLOTS_PER_REQ * bs) + bs)
 
     def _fit_chunk(self, chunk: int, bs: int, kv_tokens: int, max_len: int, max_slots: int) -> int:
-        """the split size doubles until the step's items fit the slots the launch covers"""
+        """the split size doubles until the items the host's bound allows fit the slots the launch covers (the plan
+        kernel grows it further where the device-side lengths need more)"""
         while _native.decode_plan_slots(bs, max_len, chunk, kv_tokens) > max_slots:
             chunk *= 2
         return chunk
@@ -232,60 +228,11 @@ class HipAttnBackend(AttentionBackend):
             if plans[i].numel() < need:
                 plans[i] = torch.empty(need, dtype=torch.int32, device=self.device)
             _native.decode_plan(plans[i], lens, max_len, chunk, slots, ranges)
-            if with_items:
-                self._watch_plan(plans[i], slots)
             # third field: the smallest split size this plan buffer may carry when the launch runs - the
             # step's own chunk (eager), MIN_CHUNK under graph replay (a later step's plan may use any size)
             out.append((plans[i], slots, chunk if max_slots is None else self.MIN_CHUNK, ranges))
             need_slots = max(need_slots, slots, bs + ranges if ranges else 0)
         return tuple(out), need_slots
-
-    # ---------------------------------------------------------------- plan overflow (an understated seq_lens_sum)
-    def _watch_plan(self, plan: torch.Tensor, slots: int) -> None:
-        """The plan kernel records how many items the device-side lengths need; more than the launch covers means
-        splits were dropped (wrong logits).  The header comes back through a 16-byte asynchronous copy: earlier
-        plans whose copy has landed are checked here, this one at the next plan or in check_plans().
-        With a `plan_step` (the overlap worker sets one per step, tp_worker_client.py) nothing is checked HERE: this is
-        the forward thread, and an error raised in it would end the thread instead of reaching the scheduler with the
-        step it belongs to - the entry carries the step and check_plans(upto=step) on the scheduler's side
-        reports it when that step's results are resolved."""
-        if self.plan_step is None:
-            self.check_plans(wait=len(self._plan_checks) >= 64)      # (a bound on the copies in flight)
-        with self._plan_lock:
-            host, ev = self._plan_hosts.pop() if self._plan_hosts else (
-                torch.empty(_native.PLAN_HEADER_WORDS, dtype=torch.int32, pin_memory=True), torch.cuda.Event())
-        host.copy_(plan[:_native.PLAN_HEADER_WORDS], non_blocking=True)
-        ev.record()
-        with self._plan_lock:
-            self._plan_checks.append((host, ev, slots, self.plan_step))
-        if self.strict_plan_check and self.plan_step is None:
-            self.check_plans(wait=True)
-
-    def check_plans(self, wait: bool = True, upto: Optional[int] = None) -> None:
-        """Raise RuntimeError if a decode plan built so far was cut short.  wait=False looks only at header copies
-        that have already completed (no synchronisation).  upto=N: only the plans of steps <= N (entries tagged through
-        `plan_step`); later steps' entries stay for their own check."""
-        pending = []
-        err = None
-        with self._plan_lock:
-            checks, self._plan_checks = self._plan_checks, []
-        for entry in checks:
-            host, ev, slots, step = entry
-            if upto is not None and step is not None and step > upto:
-                pending.append(entry)
-                continue
-            if wait:
-                ev.synchronize()
-            elif not ev.query():
-                pending.append(entry)
-                continue
-            err = err or _native.decode_plan_overflow(host.tolist(), slots)
-            with self._plan_lock:
-                self._plan_hosts.append((host, ev))
-        with self._plan_lock:
-            self._plan_checks = pending + self._plan_checks
-        if err:
-            raise RuntimeError(err)
 
     def _windows(self, bs, seq_lens, seq_lens_sum, encoder_lens, encoder_sum):
         """(lens, bound on their sum) of the three kv windows of a decode step"""

@@ -319,9 +319,8 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(DecodeArgs a) {
 
 // Build the step's plan.  max_items = 0 (ABI 9: the caller's launches all take the range geometry): the item section is
 // its header alone, [0, chunk, 0, 0], and only the range section behind it is built.  Otherwise the (request, split) items:
-// plan[0] = number of non-empty (request, split) items the plan lists, plan[1] = chunk,
-// plan[2] = the number the lengths NEED (> plan[0]: items were cut at max_items because the host's bound on
-// sum(seq_lens) does not hold - an error the host reports, sp_decode_plan), plan[3] = 0,
+// plan[0] = number of non-empty (request, split) items the plan lists, plan[1] = the split size they use (`chunk`, doubled
+// until the items fit max_items: ABI 10), plan[2] = the number the lengths need (= plan[0]), plan[3] = keys per kv head,
 // plan[4 + b] = first partial slot of request b (exclusive scan of its split count), the items (b, c) from
 // plan[4 + bs].  One workgroup; requests in tiles of 256 with a running offset.  Items are
 // emitted longest-first: all full splits, then the ragged last splits in four length classes (longest
@@ -333,9 +332,26 @@ __global__ __launch_bounds__(256) void decode_plan_kernel(int32_t* __restrict__ 
                                                            int max_items, int ranges) {
   __shared__ int s_scan[256];
   __shared__ int s_base;
-  __shared__ unsigned long long s_keys;
+  __shared__ unsigned long long s_keys, s_need;
   if (threadIdx.x == 0) s_keys = 0;
   int32_t* items = plan + kPlanHdr + bs;
+  // The host sizes max_items from its bound on sum(seq_lens).  Where the lengths need more items at `chunk` (the bound
+  // was understated) the split size doubles until they fit: at chunk >= max_len every non-empty request is one item and
+  // max_items >= bs (sp_decode_plan), so every split is listed.  (chunk < max_len <= 2^30 here: the doubling stays an int.)
+  while (max_items > 0) {
+    __syncthreads();
+    if (threadIdx.x == 0) s_need = 0;
+    __syncthreads();
+    unsigned long long need = 0;
+    for (int b = threadIdx.x; b < bs; b += 256) {
+      const int seq = min((int)load_idx(seq_lens, b, idx64), max_len);
+      need += seq > 0 ? (seq - 1) / chunk + 1 : 0;
+    }
+    atomicAdd(&s_need, need);
+    __syncthreads();
+    if (s_need <= (unsigned long long)max_items || chunk >= max_len) break;
+    chunk *= 2;
+  }
   // pass -1: slot0[b]; pass 0: full splits; passes 1..4: ragged tails by length class
   for (int pass = -1; pass < 5 && max_items > 0; ++pass) {
     if (pass <= 0) {
@@ -369,9 +385,7 @@ __global__ __launch_bounds__(256) void decode_plan_kernel(int32_t* __restrict__ 
       if (pass == -1) {
         if (b < bs) plan[kPlanHdr + b] = base;
       } else {
-        // (the host sizes max_items from its own bound on sum(seq_lens); lengths that break that bound
-        // lose their surplus items here, and the kernels skip slots >= max_items, instead of writing past
-        // the plan and the partials)
+        // (the chunk above makes every item fit; the bound stays as a guard of the plan and the partials)
         for (int i = 0; i < mine && base + i < max_items; ++i) {
           items[2 * (base + i)] = b;
           items[2 * (base + i) + 1] = pass == 0 ? i : nfull;
@@ -640,6 +654,8 @@ extern "C" int sp_decode_plan(int32_t* plan, size_t plan_bytes, const void* seq_
   SP_CHECK_ARG(max_seq_len >= 0 && max_seq_len <= 0x7fffffffLL && max_slots >= 0 && max_slots <= 0x3fffffffLL);
   SP_CHECK_ARG(ranges >= 0 && ranges <= 65536);
   SP_CHECK_ARG(max_slots > 0 || ranges > 0);           // (a plan with neither section plans nothing)
+  // items: room for one per request, which the plan kernel's split size reaches by doubling below 2^31
+  SP_CHECK_ARG(max_slots == 0 || (max_slots >= batch_size && max_seq_len <= (1 << 30)));
   SP_CHECK_ARG(ranges == 0 || range_line_fits(batch_size, max_seq_len));
   if (plan_bytes < sp_decode_plan_bytes(batch_size, max_slots, ranges)) return SP_ERR_WORKSPACE;
   // an empty batch: sp_decode_plan_bytes() sized no sections (16 bytes) and the launches of the step return at once

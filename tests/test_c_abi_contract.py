@@ -24,7 +24,7 @@ DT = c_header.enum_values("sp_dtype")
 def test_header_parses_into_known_types():
     protos = c_header.prototypes()
     assert len(protos) >= 40
-    assert c_header.abi_version() == 9
+    assert c_header.abi_version() == 10
     assert DT == {"SP_F32": 0, "SP_F16": 1, "SP_BF16": 2, "SP_FP8_E5M2": 3}
     assert STATUS == {"SP_OK": 0, "SP_ERR_INVALID_ARG": -1, "SP_ERR_UNSUPPORTED": -2, "SP_ERR_WORKSPACE": -3,
                       "SP_ERR_LAUNCH": -4}
@@ -266,6 +266,9 @@ def test_decode_plan_refusals(lib, addr):
         assert call(**{k: -1}) == INVALID, k
     assert call(plan_bytes=need - 1) == WORKSPACE
     assert call(max_slots=0, ranges=0) == INVALID
+    # ABI 10: an item plan has room for one item per request (the plan kernel's split size can always reach that)
+    assert call(max_slots=2) == INVALID and call(max_slots=2, ranges=0) == INVALID
+    assert call(max_seq_len=(1 << 30) + 1, ranges=0) == INVALID
 
 
 def test_extend_refusals(lib, addr):

@@ -315,22 +315,33 @@ def test_decode_split_size_travels_in_the_plan(nat, dtype):
         check_decode(o, p, 0.11, dtype, f"plan chunk {chunk}")
         if chunk == 64:
             assert torch.equal(o, ref), "same split size: same bits as the static grid"
-    # a slot budget the lengths do not fit (a broken host bound): items beyond it are dropped by the plan and
-    # the kernels never touch a slot past the workspace - no fault, the affected rows are simply incomplete
-    slots = 8
+    # a slot budget the lengths do not fit at chunk 64 (a broken host bound): the plan kernel doubles the split size
+    # until every item fits (ABI 10) - the bits of a plan built at that size with ample slots, and nothing is written
+    # past the workspace
+    slots = max(8, bs)
     ws = torch.full((nat.decode_workspace_bytes(bs, Hq, D, ctx, 64, slots) + 4096,), 0x7f, dtype=torch.uint8, device=DEV)
     plan = torch.empty(nat.decode_plan_bytes(bs, ctx, 64, slots) // 4, dtype=torch.int32, device=DEV)
     nat.decode_plan(plan, seq, ctx, 64, slots)
-    assert int(plan[0]) == slots
-    # ... and the plan says so: word 2 is what the lengths need, which the host compares with the capacity
-    assert int(plan[2]) == sum(-(-l // 64) for l in lens) > slots
-    assert "overflow" in nat.decode_plan_overflow(plan[:4].tolist(), slots)
-    assert nat.decode_plan_overflow(plan[:4].tolist(), int(plan[2])) is None
-    o = torch.zeros_like(q)
+    grown = int(plan[1])
+    assert grown > 64 and grown & (grown - 1) == 0, f"split size {grown}: 64 x 2^k"
+    assert sum(-(-l // (grown // 2)) for l in lens) > slots, "the smallest such size"
+    assert int(plan[0]) == int(plan[2]) == sum(-(-l // grown) for l in lens) <= slots
+    o = torch.full_like(q, float("nan"))
     nat.decode_attention(o, q, p["k_buffer"], p["v_buffer"], p["req_to_token"], req, seq, 0.11, 0.0,
                          ctx, 64, ws[:nat.decode_workspace_bytes(bs, Hq, D, ctx, 64, slots)], None, plan, max_slots=slots)
     torch.cuda.synchronize()
     assert bool((ws[-4096:] == 0x7f).all()), "nothing written past the workspace"
+    check_decode(o, p, 0.11, dtype, f"split size grown to {grown}")
+    ample = nat.decode_plan_slots(bs, ctx, grown, kv_tokens=sum(lens))
+    ws = torch.empty(nat.decode_workspace_bytes(bs, Hq, D, ctx, 64, ample), dtype=torch.uint8, device=DEV)
+    ref_plan = torch.empty(nat.decode_plan_bytes(bs, ctx, 64, ample) // 4, dtype=torch.int32, device=DEV)
+    nat.decode_plan(ref_plan, seq, ctx, grown, ample)
+    n = 4 + bs + 2 * int(plan[0])
+    assert torch.equal(plan[:n].cpu(), ref_plan[:n].cpu()), "the plan of that split size, item for item"
+    o_ref = torch.full_like(q, float("nan"))
+    nat.decode_attention(o_ref, q, p["k_buffer"], p["v_buffer"], p["req_to_token"], req, seq, 0.11, 0.0,
+                         ctx, 64, ws, None, ref_plan, max_slots=ample)
+    assert torch.equal(o, o_ref), "the bits of a plan built at the grown split size with ample slots"
 
 
 def test_decode_rejects_bad_arguments(nat):
@@ -706,7 +717,6 @@ def test_backend_plans_items_only_for_a_model_with_a_soft_cap_layer(nat):
     oc = be.forward_decode(q, None, None, capped, fb, save_kv_cache=False).view(bs, Hq, D)
     assert nat.debug_get("decode_last_kernel") in ITEM_KERNELS
     check_decode(oc, p, D ** -0.5, dtype, "capped layer on the items", cap=20.0)
-    be.check_plans()
 
 
 def test_random_shapes_decode_and_extend_against_oracle(nat):

@@ -456,7 +456,8 @@ def test_decode_split_size_policy_and_where_items_are_planned():
     """HipAttnBackend host logic only.  (a) _plan_chunk: about one (request, split) item per CU between MIN_CHUNK and
     MAX_CHUNK, from the host's bound on sum(seq_lens) alone (the advisory longest-request hint left in round 6).
     (b) which plans carry items at all: only where a launch of the model can read them - a shape the range kernel refuses
-    (decode_ranges 0), a layer with a logit soft-cap, or a step whose line does not fit the range section."""
+    (decode_ranges 0), a layer with a logit soft-cap, or a step whose line does not fit the range section.  Under graph
+    replay that line is the largest bucket's: every bucket's launches take its piece count."""
     from scratchpad_amd.attention import HipAttnBackend
     b = HipAttnBackend.__new__(HipAttnBackend)
     b.num_kv_head, b.head_dim = 8, 128
@@ -476,6 +477,16 @@ def test_decode_split_size_policy_and_where_items_are_planned():
     assert b._graph_slots(16) == b.GRAPH_SLOTS_FLOOR + 16
     b.decode_ranges, b.max_context_len = 256, 2 ** 24            # bs x (context + 16) >= 2^31: the line does not fit
     assert b._ranges_for(256, 2 ** 24) == 0 and b._graph_slots(256) > 0
+    # ... for the largest bucket but not for a smaller one: the captured launches of every bucket take no range pieces
+    # (init_cuda_graph_state decides them for max_bs), so the smaller bucket needs its items too
+    assert b._ranges_for(64, 2 ** 24) == 256 and b._graph_slots(64) == 0
+    b._graph_ranges = b._ranges_for(256, b.max_context_len)
+    assert b._graph_ranges == 0
+    assert b._graph_slots(64) == min(64 * -(-2 ** 24 // b.MIN_CHUNK), b.GRAPH_SLOTS_FLOOR + 64) > 0
+    assert b._graph_slots(256) > 0
+    b.max_context_len = 8192                                     # a line every bucket fits: no items
+    b._graph_ranges = b._ranges_for(256, b.max_context_len)
+    assert b._graph_ranges == 256 and b._graph_slots(64) == 0 and b._graph_slots(256) == 0
 
 
 def test_plan_registry_trusts_only_live_plan_buffers():
