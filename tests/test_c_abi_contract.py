@@ -247,6 +247,10 @@ def test_decode_refusals(lib, addr):
     assert call(workspace=None) == WORKSPACE
     assert call(head_dim=96) == UNSUPPORTED
     assert call(dtype=DT["SP_F32"], kv_dtype=DT["SP_FP8_E5M2"]) == UNSUPPORTED
+    # the kernels form a key's address as base + slot * token stride with the stride held in 32 bits: a token stride
+    # of 2^32 bytes or more is refused (bf16: the stride is in elements, the byte pool's in bytes)
+    assert call(kv_buffer_stride=2 ** 31) == INVALID
+    assert call(kv_buffer_stride=2 ** 32, kv_dtype=DT["SP_FP8_E5M2"]) == INVALID
     # a plan one byte short of sp_decode_plan_bytes(batch_size, max_slots, ranges), for each kind of plan
     for slots, ranges in ((6, 0), (6, 32), (0, 32)):
         need = c_header.call(lib, "sp_decode_plan_bytes", batch_size=3, max_slots=slots, ranges=ranges)

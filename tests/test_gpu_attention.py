@@ -33,12 +33,12 @@ def decode_kernel(request, nat):
 
 
 def run_decode(nat, p, scale, cap=0.0, chunk=64, max_len=None, kv_start=None, idx_dtype=None, use_plan=True, ranges=0,
-               items=True):
+               items=True, k_scale=None, v_scale=None):
     """use_plan (what HipAttnBackend does): the per-step plan + the separate merge launch; without: the static
     (request, split) grid.  ranges > 0: the plan carries the range geometry with that many pieces and the launch is given
     it - THE SHIPPED FORM where the range kernel takes the launch (HipAttnBackend passes sp_decode_ranges()).
     items=False: the plan is built WITHOUT the (request, split) items (max_slots = 0), as the backend builds it for a model
-    whose layers all take the range kernel."""
+    whose layers all take the range kernel.  k_scale / v_scale: the layer scales of a byte pool."""
     q = p["q"]
     bs, Hq, D = q.shape
     seq, req = p["seq_lens"], p["req_pool_indices"]
@@ -54,7 +54,8 @@ def run_decode(nat, p, scale, cap=0.0, chunk=64, max_len=None, kv_start=None, id
         plan = torch.empty(nat.decode_plan_bytes(bs, max_len, chunk, slots, ranges) // 4, dtype=torch.int32, device=DEV)
         nat.decode_plan(plan, seq, max_len, chunk, slots, ranges)
     nat.decode_attention(o, q, p["k_buffer"], p["v_buffer"], p["req_to_token"], req, seq, scale, cap,
-                         max_len, chunk, ws, kv_start, plan, max_slots=slots, ranges=ranges)
+                         max_len, chunk, ws, kv_start, plan, k_scale=k_scale, v_scale=v_scale, max_slots=slots,
+                         ranges=ranges)
     return o
 
 
@@ -357,12 +358,13 @@ def test_decode_rejects_bad_arguments(nat):
 
 # ----------------------------------------------------------------------------------- extend
 def run_extend(nat, q, kb, vb, r2t, req, seq, ext, start, scale, cap=0.0, causal=True, kv_start=None,
-               window_left=-1, plan=None):
+               window_left=-1, plan=None, k_scale=None, v_scale=None):
     T_, Hq, D = q.shape
     ws = torch.empty(nat.extend_workspace_bytes(T_, len(seq), Hq, D, q.dtype), dtype=torch.uint8, device=DEV)
     o = torch.full_like(q, float("nan"))
     nat.extend_attention(o, q, kb, vb, r2t, req, seq, ext, start, scale, cap, causal,
-                         int(ext.max()), int(seq.max()), ws, kv_start, window_left=window_left, plan=plan)
+                         int(ext.max()), int(seq.max()), ws, kv_start, window_left=window_left, k_scale=k_scale,
+                         v_scale=v_scale, plan=plan)
     return o
 
 
