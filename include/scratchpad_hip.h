@@ -306,7 +306,9 @@ SP_API int sp_extend_attention(void* out, const void* q, const void* k_buffer, c
  * sp_top_k_top_p_min_p_sample draws, per row, the token whose interval of the kept cumulative
  * mass (token-id order) contains floor(uniform * kept_mass); uniform[b] in [0,1) is supplied by
  * the caller (sampler.py:87-90 draws them with torch.rand).  keep_count (nullable) receives the
- * number of kept tokens per row.  A row with no mass yields token 0.
+ * number of kept tokens per row.  A row with no mass yields token 0.  NaN and entries <= 0 rank as
+ * zero (after every positive entry, by token id), carry no mass and renormalise to 0; a top_k <= 0
+ * keeps nothing.
  * sp_argmax returns the first maximal index (torch.argmax).                                       */
 SP_API int sp_argmax(const void* logits, int64_t row_stride, int batch_size, int vocab, int64_t* out_ids,
               int dtype, void* stream);

@@ -15,8 +15,8 @@
 // same token from the same probabilities (what sampler.py:146-157 asks of the kernels).
 // The row (513 KB at vocab 128256) stays in the XCD's L2 between passes; HBM sees it once.
 //
-// tests/test_gpu_sampling.py holds the kernels to the CPU statement of the same definition,
-// exactly (ids, keep counts).
+// tests/test_gpu_sampling.py and tests/test_gpu_sampling_rows.py hold the kernels to the CPU statement
+// of the same definition, exactly (ids, keep counts), the latter on every row of tie-heavy batches.
 #include "sp_common.h"
 
 namespace sp {
@@ -275,7 +275,8 @@ __global__ __launch_bounds__(kSampThreads) void select_kernel(SelectArgs a) {
       const uint64_t tmask = __ballot(tie);
       const uint32_t rank = ties_before + __popcll(tmask & ((1ull << lane) - 1));
       const bool keep = bits > cut.pivot || (tie && rank < cut.ties_kept);
-      if (i < hi) out[i] = (keep && cut.total) ? p / denom : 0.f;
+      // as_f32(bits), not p: a kept bad entry (NaN, negative: they rank as zero) renormalises to 0
+      if (i < hi) out[i] = (keep && cut.total) ? as_f32(bits) / denom : 0.f;
       ties_before += __popcll(tmask);
     }
   }

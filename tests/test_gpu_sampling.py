@@ -127,6 +127,10 @@ def test_full_vocab_rows_against_oracle_and_properties():
         keep, _ = osamp.select(pn[b], int(ks[b]), float(ps[b]), float(ms[b]))
         assert int(cnt[b]) == int(keep.sum()), b
         assert int(ids[b]) == osamp.sample(pn[b], int(ks[b]), float(ps[b]), float(ms[b]), float(u[b])), b
+    # all 64 rows through the vectorised oracle (tests/test_oracle_sampling_rows.py: equal to the loop form)
+    selected = osamp.select_rows(pn, ks.numpy(), ps.numpy(), ms.numpy())
+    assert np.array_equal(cnt.numpy(), selected[0].sum(-1))
+    assert np.array_equal(ids.numpy(), osamp.sample_rows(pn, ks.numpy(), ps.numpy(), ms.numpy(), u.numpy(), selected))
 
 
 def test_degenerate_rows():
