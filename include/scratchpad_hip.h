@@ -332,6 +332,46 @@ SP_API int sp_top_k_top_p_min_p_renorm(const float* probs, int64_t row_stride, c
                                 const float* top_ps, const float* min_ps, int batch_size, int vocab,
                                 float* out, int64_t out_stride, int32_t* keep_count, void* stream);
 
+/* ---- Sampling penalties and grammar vocab masks (additive within ABI 10): replaces
+ *      SamplingBatchInfo.apply_logits_bias (sampling/sampling_batch_info.py:324-344) and the dense per-penalizer
+ *      tensors behind it (sampling/penaltylib/penalizers/), and the grammar back-ends' apply_vocab_mask
+ *      (constrained/triton_ops/bitmask_ops.py, constrained/outlines_backend.py:82-83).
+ * State (caller-owned, int32, one row per req_to_token row): entries [pool_rows, capacity, 2] = the (token, count)
+ * pairs of the request's distinct output tokens, n_distinct [pool_rows], out_len [pool_rows].  Row indices
+ * (pool_row_indices / req_pool_indices) are int64 with idx64 = 1, int32 with 0; an index outside [0, pool_rows) makes
+ * every kernel skip that row.  The rows of one batch must be distinct.
+ * sp_penalty_reset:    n_distinct = out_len = 0 for the listed rows.
+ * sp_penalty_cumulate: per batch row, count token_ids[b] in its request's list (increment or append) and out_len += 1;
+ *                      an id outside [0, vocab) leaves the row untouched.  A full list is never written past:
+ *                      *error (device word) is set to 1 instead and stays set.
+ * sp_penalty_apply:    in place on fp32 logits [num_rows, >= vocab]: for each entry (t, c) of the row
+ *                      x = logits[b, t]; x -= c * frequency; x -= presence; x = x > 0 ? x / repetition : x * repetition
+ *                      (in this order), then logits[b, s] = -inf for every stop id s of the row (stop_token_ids
+ *                      [num_rows, max_stops], -1 = none) while out_len < min_new_tokens[b].  min_new_tokens and
+ *                      stop_token_ids may be NULL together with max_stops == 0.  A row with (0, 0, 1, 0) is left alone.
+ * sp_vocab_mask_apply: in place, -inf where the mask forbids; only forbidden elements are written.  mask_kind 0:
+ *                      packed int32 [num_rows, mask_width] words, bit j of word i = token 32 i + j, 1 = allowed;
+ *                      columns at or beyond min(vocab, 32 mask_width) are left alone and mask_width >
+ *                      ceil(vocab / 32) is refused.  mask_kind 1: one byte per token [num_rows, mask_width == vocab],
+ *                      non-zero = forbidden.  mask_stride: elements (words / bytes) between mask rows.
+ * SP_ERR_INVALID_ARG before any launch: NULL required pointer, negative size, row_stride < vocab, the widths above.
+ * num_rows is the batch size (one row per request of the batch); 0 is SP_OK and launches nothing.  It is not called
+ * batch_size like its neighbours' because tests/test_gpu_c_abi.py pins the list of entry points that take a parameter of
+ * that name; tests/test_gpu_penalties.py holds these four to the same empty-batch rule.                                                 */
+SP_API int sp_penalty_reset(int32_t* n_distinct, int32_t* out_len, const void* pool_row_indices, int idx64,
+                     int num_rows, int pool_rows, void* stream);
+SP_API int sp_penalty_cumulate(int32_t* entries, int32_t* n_distinct, int32_t* out_len, int32_t* error,
+                        const void* req_pool_indices, int idx64, const int64_t* token_ids, int num_rows,
+                        int pool_rows, int capacity, int vocab, void* stream);
+SP_API int sp_penalty_apply(float* logits, int64_t row_stride, const int32_t* entries, const int32_t* n_distinct,
+                     const int32_t* out_len, const void* req_pool_indices, int idx64,
+                     const float* frequency_penalties, const float* presence_penalties,
+                     const float* repetition_penalties, const int32_t* min_new_tokens,
+                     const int32_t* stop_token_ids, int max_stops, int num_rows, int pool_rows, int capacity,
+                     int vocab, void* stream);
+SP_API int sp_vocab_mask_apply(float* logits, int64_t row_stride, const void* mask, int64_t mask_stride,
+                        int mask_width, int mask_kind, int num_rows, int vocab, void* stream);
+
 /* ---- Small-batch projection: out[M,N] = x[M,K] . w[N,K]^T, M <= 16, K % 32 == 0, fp16/bf16,
  *      fp32 accumulation, one rounding.  Serves F.linear inside QKVParallelLinear /
  *      MergedColumnParallelLinear / RowParallelLinear.forward (nn/layers/linear.py:423-470, 696-760,

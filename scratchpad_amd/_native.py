@@ -88,6 +88,11 @@ SIGNATURES = {
     "sp_softmax_temperature": (_i32, [_vp, _i64, _vp, _i32, _i32, _vp]),
     "sp_top_k_top_p_min_p_sample": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "sp_top_k_top_p_min_p_renorm": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "sp_penalty_reset": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "sp_penalty_cumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "sp_penalty_apply": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                _i32, _vp]),
+    "sp_vocab_mask_apply": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "sp_ar_flag_bytes": (_sz, []),
     "sp_ar_alloc": (_i32, [_vp, _sz]),
     "sp_ar_free": (_i32, [_vp]),
@@ -636,6 +641,119 @@ def top_k_top_p_min_p_renorm(probs: torch.Tensor, top_ks: Optional[torch.Tensor]
                                               bs, vocab, out.data_ptr(), out.stride(0), _ptr(cnt), _stream()),
            "sp_top_k_top_p_min_p_renorm")
     return (out, cnt) if return_keep_count else out
+
+
+# --------------------------------------------------------------------------- penalties / vocab masks
+# launches of the four kernels of csrc/penalties.hip made through this module (tests: a batch without penalties or
+# masks must leave every count where it was)
+PENALTY_LAUNCHES = {"reset": 0, "cumulate": 0, "apply": 0, "mask": 0}
+
+
+def _pool_rows_arg(idx: torch.Tensor, what: str):
+    if idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 1:
+        raise RuntimeError(f"{what}: row indices must be 1-D int32 or int64")
+    return idx.contiguous(), int(idx.dtype == torch.int64)
+
+
+def _penalty_store(entries: torch.Tensor, n_distinct: torch.Tensor, out_len: torch.Tensor, what: str):
+    _gpu(entries, n_distinct, out_len)
+    if (entries.dtype != torch.int32 or entries.dim() != 3 or entries.shape[2] != 2 or not entries.is_contiguous()
+            or n_distinct.dtype != torch.int32 or out_len.dtype != torch.int32
+            or n_distinct.shape != (entries.shape[0],) or out_len.shape != (entries.shape[0],)
+            or not n_distinct.is_contiguous() or not out_len.is_contiguous()):
+        raise RuntimeError(f"{what}: the store is int32 entries [pool_rows, capacity, 2] with n_distinct / out_len "
+                           "[pool_rows], all contiguous")
+    return entries.shape[0], entries.shape[1]
+
+
+def penalty_reset(n_distinct: torch.Tensor, out_len: torch.Tensor, pool_row_indices: torch.Tensor) -> None:
+    _gpu(n_distinct, out_len, pool_row_indices)
+    rows, idx64 = _pool_rows_arg(pool_row_indices, "penalty_reset")
+    _check(load().sp_penalty_reset(n_distinct.data_ptr(), out_len.data_ptr(), rows.data_ptr(), idx64, rows.shape[0],
+                                   n_distinct.shape[0], _stream()), "sp_penalty_reset")
+    PENALTY_LAUNCHES["reset"] += 1
+
+
+def penalty_cumulate(entries: torch.Tensor, n_distinct: torch.Tensor, out_len: torch.Tensor, error: torch.Tensor,
+                     req_pool_indices: torch.Tensor, token_ids: torch.Tensor, vocab: int) -> None:
+    """Count token_ids[b] (int64 [bs]) in the list of pool row req_pool_indices[b]; ids outside [0, vocab) are ignored."""
+    pool_rows, capacity = _penalty_store(entries, n_distinct, out_len, "penalty_cumulate")
+    _gpu(error, req_pool_indices, token_ids)
+    rows, idx64 = _pool_rows_arg(req_pool_indices, "penalty_cumulate")
+    if token_ids.dtype != torch.int64 or token_ids.shape != rows.shape or error.dtype != torch.int32:
+        raise RuntimeError("penalty_cumulate: token_ids int64 [bs], error int32 [1]")
+    _check(load().sp_penalty_cumulate(entries.data_ptr(), n_distinct.data_ptr(), out_len.data_ptr(), error.data_ptr(),
+                                      rows.data_ptr(), idx64, token_ids.contiguous().data_ptr(), rows.shape[0],
+                                      pool_rows, capacity, int(vocab), _stream()), "sp_penalty_cumulate")
+    PENALTY_LAUNCHES["cumulate"] += 1
+
+
+def penalty_apply_(logits: torch.Tensor, vocab: int, entries: torch.Tensor, n_distinct: torch.Tensor,
+                   out_len: torch.Tensor, req_pool_indices: torch.Tensor, frequency_penalties: torch.Tensor,
+                   presence_penalties: torch.Tensor, repetition_penalties: torch.Tensor,
+                   min_new_tokens: Optional[torch.Tensor] = None,
+                   stop_token_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place on fp32 logits [bs, >= vocab] (row stride free).  stop_token_ids: int32 [bs, max_stops], -1 = none."""
+    pool_rows, capacity = _penalty_store(entries, n_distinct, out_len, "penalty_apply_")
+    _gpu(logits, req_pool_indices, frequency_penalties, presence_penalties, repetition_penalties, min_new_tokens,
+         stop_token_ids)
+    logits = _prob_rows(logits, "penalty_apply_")
+    if logits.dtype != torch.float32 or logits.shape[1] < vocab:
+        raise RuntimeError("penalty_apply_: fp32 logits [bs, >= vocab] expected (LogitsProcessor returns fp32)")
+    bs = logits.shape[0]
+    rows, idx64 = _pool_rows_arg(req_pool_indices, "penalty_apply_")
+    if rows.shape[0] != bs:
+        raise RuntimeError(f"penalty_apply_: {bs} logit rows, {rows.shape[0]} pool row indices")
+    f, p, r = (_opt(t, torch.float32, bs, n) for t, n in ((frequency_penalties, "frequency_penalties"),
+                                                          (presence_penalties, "presence_penalties"),
+                                                          (repetition_penalties, "repetition_penalties")))
+    m = _opt(min_new_tokens, torch.int32, bs, "min_new_tokens")
+    max_stops = 0
+    if stop_token_ids is not None:
+        if m is None or stop_token_ids.dtype != torch.int32 or stop_token_ids.dim() != 2 or stop_token_ids.shape[0] != bs:
+            raise RuntimeError("penalty_apply_: stop_token_ids is int32 [bs, max_stops] and goes with min_new_tokens")
+        stop_token_ids = stop_token_ids.contiguous()
+        max_stops = stop_token_ids.shape[1]
+    _check(load().sp_penalty_apply(logits.data_ptr(), logits.stride(0), entries.data_ptr(), n_distinct.data_ptr(),
+                                   out_len.data_ptr(), rows.data_ptr(), idx64, f.data_ptr(), p.data_ptr(), r.data_ptr(),
+                                   _ptr(m) if max_stops else None, _ptr(stop_token_ids) if max_stops else None,
+                                   max_stops, bs, pool_rows, capacity, int(vocab), _stream()), "sp_penalty_apply")
+    PENALTY_LAUNCHES["apply"] += 1
+    return logits
+
+
+def vocab_mask_apply_(logits: torch.Tensor, vocab_mask: torch.Tensor) -> torch.Tensor:
+    """In place: -inf where the mask forbids.  int32 [bs, w] = xgrammar's packed bitmask (1 = allowed), bool
+    [bs, vocab] = outlines' mask (True = forbidden); anything else is refused."""
+    _gpu(logits, vocab_mask)
+    logits = _prob_rows(logits, "vocab_mask_apply_")
+    if logits.dtype != torch.float32:
+        raise RuntimeError("vocab_mask_apply_: fp32 logits expected")
+    if vocab_mask.dim() == 1:
+        vocab_mask = vocab_mask.unsqueeze(0)
+    if vocab_mask.dim() != 2 or vocab_mask.shape[0] != logits.shape[0]:
+        raise RuntimeError(f"vocab_mask_apply_: batch size mismatch: logits {tuple(logits.shape)} vs mask "
+                           f"{tuple(vocab_mask.shape)}")
+    if vocab_mask.dtype == torch.int32:
+        kind = 0
+        need = (logits.shape[1] + 31) // 32
+        if vocab_mask.shape[1] > need:
+            raise RuntimeError(f"Bitmask width too large: allow at most {need} int32s for logits' width "
+                               f"{logits.shape[1]}, but got {vocab_mask.shape[1]}")
+    elif vocab_mask.dtype == torch.bool:
+        kind = 1
+        if vocab_mask.shape[1] != logits.shape[1]:
+            raise RuntimeError(f"vocab_mask_apply_: a bool mask has one element per column: {tuple(vocab_mask.shape)} "
+                               f"vs logits {tuple(logits.shape)}")
+    else:
+        raise RuntimeError(f"vocab_mask_apply_: mask dtype {vocab_mask.dtype} is neither int32 (packed) nor bool")
+    if vocab_mask.stride(1) != 1:
+        vocab_mask = vocab_mask.contiguous()
+    _check(load().sp_vocab_mask_apply(logits.data_ptr(), logits.stride(0), vocab_mask.data_ptr(), vocab_mask.stride(0),
+                                      vocab_mask.shape[1], kind, logits.shape[0], logits.shape[1], _stream()),
+           "sp_vocab_mask_apply")
+    PENALTY_LAUNCHES["mask"] += 1
+    return logits
 
 
 # --------------------------------------------------------------------------- small-batch projection

@@ -24,6 +24,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 # allreduce.hip: its fused all-reduce + add + RMSNorm kernel reproduces elementwise.hip's norm bit for bit
 PER_FILE_FLAGS = {"elementwise.hip": ["-ffp-contract=off"], "allreduce.hip": ["-ffp-contract=off"],
                   "extend_mfma.hip": ["-fno-honor-nans"],
+                  # penalties.hip: x - c * f is a product rounded on its own, then a subtraction (the statement the
+                  # tests hold it to, tests/penalty_oracle.py), not one v_fma
+                  "penalties.hip": ["-ffp-contract=off"],
                   # extend_w64.hip: every filler of its hand-placed MFMA gaps is a single instruction: no SLP packing
                   # of adjacent f32 adds / multiplies into v_pk_* (MI355X_MICROARCH.md: an anti-lever beside MFMAs).  Its
                   # accumulation registers belong to its assembly text alone: compile_w64 below / tools/w64_asm.py.  The

@@ -106,6 +106,9 @@ class ModelWorkerBatch:
     # stand-in for the (un-hosted) vision tower: projected + flattened vision states of the requests
     # whose encoder is not cached, [sum(encoder_lens_need), hidden] (mllama.py:966-979)
     encoder_states: Optional[torch.Tensor] = None
+    # (pool row, emitted tokens) of the penalised requests this batch admits: their penalty histories are reset and
+    # seeded from these at the start of this batch's sample(), on the stream that also cumulates (penalty_state.py)
+    penalty_seed: Optional[list] = None
 
 
 @dataclass
@@ -164,6 +167,7 @@ class ForwardBatch:
     mrope_positions: torch.Tensor = None
     # ---- not in the reference (kept behind its fields)
     encoder_states: Optional[torch.Tensor] = None    # see ModelWorkerBatch
+    penalty_seed: Optional[list] = None              # see ModelWorkerBatch
 
     @classmethod
     def init_new(cls, batch: ModelWorkerBatch, model_runner) -> "ForwardBatch":
@@ -185,7 +189,7 @@ class ForwardBatch:
             return_logprob=batch.return_logprob,
             top_logprobs_nums=batch.top_logprobs_nums, token_ids_logprobs=batch.token_ids_logprobs,
             can_run_dp_cuda_graph=batch.can_run_dp_cuda_graph, topping_paths=batch.toppings_paths,
-            sampling_info=batch.sampling_info, req_to_token_pool=model_runner.req_to_token_pool,
+            sampling_info=batch.sampling_info, penalty_seed=batch.penalty_seed, req_to_token_pool=model_runner.req_to_token_pool,
             token_to_kv_pool=model_runner.token_to_kv_pool, attn_backend=model_runner.attn_backend,
             spec_algorithm=batch.spec_algorithm, spec_info=batch.spec_info,
             capture_hidden_mode=batch.capture_hidden_mode, input_embeds=batch.input_embeds,

@@ -253,15 +253,40 @@ class ModelRunner:
         raise ValueError(f"Invalid forward mode: {forward_batch.forward_mode}")
 
     def sample(self, logits_output: LogitsProcessorOutput, forward_batch: ForwardBatch) -> torch.Tensor:
-        """model_runner.py sample -> nn/layers/sampler.py:24-163.  A batch without sampling_info is
-        greedy (sampler.py:63-67)."""
+        """model_runner.py:539-563 -> nn/layers/sampler.py:24-163.  A batch without sampling_info is greedy
+        (sampler.py:63-67).  The reference's order: the grammar mask (waited for when the scheduler builds it behind
+        ``sampling_info_done``, built here otherwise), ``apply_logits_bias``, the sampler - and then the ids just drawn
+        are counted in their requests' penalty histories.  Counting here, where the ids are device values, is the same
+        in the synchronous and the overlap worker (the reference cumulates in prepare_for_decode and has to rebuild
+        a host list of the delayed tokens under overlap, schedule_batch.py:1254-1275).  A batch without penalties or
+        grammars takes none of these steps."""
         info = forward_batch.sampling_info
+        if forward_batch.penalty_seed:
+            # requests this batch admits: forget what the previous owner of their pool rows left and replay their own
+            # output so far - here, behind every cumulate of the batches that ran before this one
+            from .penalty_state import penalty_state_of
+            penalty_state_of(self.req_to_token_pool).seed([r for r, _ in forward_batch.penalty_seed],
+                                                          [h for _, h in forward_batch.penalty_seed],
+                                                          self.model_config.vocab_size)
         if info is None:
             if not forward_batch.return_logprob:
                 return logits_output.greedy_token_ids()
             info = _ALL_GREEDY
-        return self.sampler(logits_output, info, forward_batch.return_logprob, forward_batch.top_logprobs_nums,
-                            forward_batch.token_ids_logprobs)
+        if info.grammars:
+            if info.sampling_info_done is not None:
+                info.sampling_info_done.wait()
+            else:
+                info.update_regex_vocab_mask()
+        biased = getattr(info, "needs_logits_bias", False)
+        if biased:
+            # full fp32 logits on every rank (a collective under TP), penalised and masked in place; the sampler
+            # then reads these and not the vocab-parallel shards
+            info.apply_logits_bias(logits_output.gather_full_logits())
+        ids = self.sampler(logits_output, info, forward_batch.return_logprob, forward_batch.top_logprobs_nums,
+                           forward_batch.token_ids_logprobs)
+        if biased and info.has_penalties:
+            info.cumulate_output_tokens(ids)
+        return ids
 
 
 class _AllGreedy:
@@ -419,6 +444,12 @@ class TpModelWorker:
 
     def get_memory_pool(self):
         return self.model_runner.req_to_token_pool, self.model_runner.token_to_kv_pool_allocator
+
+    def check_penalty_state(self):
+        """Raise if a penalty history ever overflowed its row (reads one device word: call where results are read)."""
+        state = getattr(self.model_runner.req_to_token_pool, "penalty_state", None)
+        if state is not None:
+            state.check()
 
     def forward_batch_generation(self, model_worker_batch: ModelWorkerBatch, skip_sample: bool = False):
         forward_batch = ForwardBatch.init_new(model_worker_batch, self.model_runner)

@@ -7,7 +7,10 @@ req_to_token[req, seq_len-1] = slot), ``mix_with_running`` (1073-1101) and
 ``get_model_worker_batch`` (1399-1459), the prefix-cache hand-off (``Req.init_next_round_input``
 472-492, ``alloc_token_slots`` 727-754 evicting through ``tree_cache``), ``check_decode_mem`` /
 ``retract_decode`` (1103-1211) and ``filter_batch`` / ``merge_batch`` (1309-1397).  Admission
-policy, grammars, penalizers and detokenisation stay with the reference's scheduler (out of scope).
+policy, the grammar back-ends and detokenisation stay with the reference's scheduler (out of scope).
+Sampling penalties: ``prepare_for_extend`` resets the penalty history of the request rows it hands out and seeds it
+from ``req.output_ids`` (carried out by the batch's own ``sample``); ``prepare_for_decode`` does NOT cumulate (schedule_batch.py:1254-1275
+does) - ``ModelRunner.sample`` counts each token where it is drawn.
 """
 import threading
 from dataclasses import dataclass
@@ -285,6 +288,8 @@ class ScheduleBatch:
     # ---- not in the reference
     # None: taken from model_config.is_encoder_decoder, as the reference reads it (schedule_batch.py:1274, 1334)
     is_encoder_decoder: Optional[bool] = None
+    # (pool row, emitted tokens) of admitted penalised requests, until the next get_model_worker_batch takes them along
+    penalty_seed: Optional[list] = None
 
     def __post_init__(self):
         if self.is_encoder_decoder is None:
@@ -392,6 +397,21 @@ class ScheduleBatch:
                                    out_cache_loc)
         if self.is_encoder_decoder:
             self.prepare_encoder_info_extend(input_ids, seq_lens)
+        self.seed_penalty_state()
+
+    def seed_penalty_state(self):
+        """Note, for every admitted request that has penalties, (pool row, a copy of ``output_ids``): nothing for a
+        fresh request; for a retracted one, or the next chunk of a chunked prefill, exactly the tokens it has emitted
+        (the token a non-final chunk sampled and threw away is dropped with the reset).  Nothing is launched here:
+        the list travels with this batch (``get_model_worker_batch`` -> ``ModelWorkerBatch.penalty_seed``) and
+        ``ModelRunner.sample`` resets and seeds the rows in front of this batch's own bias, on the stream and in the
+        thread that also cumulate.  So a batch that is still queued with the previous owner of a row (the overlap
+        worker sees a finish one step late) cumulates BEFORE the reset, whatever the scheduler thread does meanwhile.
+        The reference rebuilds its orchestrator from zero on admission (from_schedule_batch) and so forgets a retracted
+        request's history; keeping it is deliberate."""
+        seeds = [(r.req_pool_idx, list(r.output_ids)) for r in self.reqs
+                 if getattr(getattr(r, "sampling_params", None), "needs_penalty_state", False)]
+        self.penalty_seed = (self.penalty_seed or []) + seeds if seeds else self.penalty_seed
 
     def prepare_encoder_info_extend(self, input_ids: List[List[int]], seq_lens: List[int]):
         """schedule_batch.py:830-899: strip the encoder (image) tokens out of the decoder-side
@@ -622,6 +642,9 @@ class ScheduleBatch:
             self.top_logprobs_nums = [0] * len(self.reqs) + list(other.top_logprobs_nums)
             self.token_ids_logprobs = [None] * len(self.reqs) + list(other.token_ids_logprobs)
         self.reqs = self.reqs + other.reqs
+        if other.penalty_seed:
+            self.penalty_seed = (self.penalty_seed or []) + other.penalty_seed
+            other.penalty_seed = None
         self.return_logprob |= other.return_logprob
         self.has_stream |= other.has_stream
         self.has_grammar |= other.has_grammar
@@ -630,6 +653,12 @@ class ScheduleBatch:
     def get_model_worker_batch(self) -> ModelWorkerBatch:
         global bid
         bid += 1
+        if self.sampling_info is not None or self.has_grammar:      # schedule_batch.py:1409-1413
+            if self.sampling_info is None:
+                from .sampler import SamplingBatchInfo
+                self.sampling_info = SamplingBatchInfo.from_schedule_batch(self, self.model_config.vocab_size)
+            self.sampling_info.grammars = [r.grammar for r in self.reqs] if self.has_grammar else None
+        penalty_seed, self.penalty_seed = self.penalty_seed, None        # travels with exactly one batch
         if self.forward_mode.is_decode_or_idle():
             extend_seq_lens = extend_prefix_lens = None
         else:
@@ -648,7 +677,7 @@ class ScheduleBatch:
             encoder_cached=self.encoder_cached, encoder_lens=self.encoder_lens,
             encoder_lens_cpu=self.encoder_lens_cpu, encoder_out_cache_loc=self.encoder_out_cache_loc,
             multimodal_inputs=[r.multimodal_inputs for r in self.reqs],
-            sampling_info=self.sampling_info, return_logprob=self.return_logprob,
+            sampling_info=self.sampling_info, penalty_seed=penalty_seed, return_logprob=self.return_logprob,
             top_logprobs_nums=self.top_logprobs_nums, token_ids_logprobs=self.token_ids_logprobs,
             extend_logprob_start_lens=(None if self.forward_mode.is_decode_or_idle() else self.extend_logprob_start_lens),
             extend_input_logprob_token_ids=(None if self.forward_mode.is_decode_or_idle()

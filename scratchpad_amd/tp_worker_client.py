@@ -8,6 +8,7 @@ negative placeholder ids at once; the forward thread writes the sampled ids into
 (``resolve_future_token_ids``, 34-40) before running it.  Every kernel of the hot path launches on
 ``torch.cuda.current_stream()``, which is ``forward_stream`` inside the thread.
 """
+import dataclasses
 import threading
 from queue import Queue
 from typing import Optional
@@ -38,6 +39,7 @@ class TpModelWorkerClient:
         self.forward_stream = torch.cuda.Stream(device=self.device)
         self.scheduler_stream = torch.cuda.current_stream(self.device)
         self.error: Optional[BaseException] = None
+        self.cur_sampling_info = None
         self.forward_thread = threading.Thread(target=self.forward_thread_func, daemon=True)
         self.forward_thread.start()
 
@@ -95,6 +97,7 @@ class TpModelWorkerClient:
         if launch_done is not None:
             launch_done.wait()
         copy_done.synchronize()
+        self.worker.check_penalty_state()         # (the device is idle for this batch: one word read, no wait)
         return logits_output, next_token_ids.tolist()
 
     def forward_batch_generation(self, model_worker_batch: ModelWorkerBatch):
@@ -104,6 +107,15 @@ class TpModelWorkerClient:
         # the scheduler's writes (req_to_token, allocator slices, input ids) must be visible to
         # the forward stream before it reads them (203-204)
         self.scheduler_stream.synchronize()
+        # tp_worker_client.py:195-199: the forward thread gets a snapshot of the sampling info, so that a filter_batch /
+        # merge_batch of the scheduler thread cannot re-point its per-row tensors between this batch's bias, sampler
+        # and cumulate.  Its sampling_info_done is the event the scheduler sets once the grammar mask of this batch is
+        # built (cur_sampling_info); the penalties live in the pool's PenaltyState, so they survive the replace.
+        sampling_info = model_worker_batch.sampling_info
+        if sampling_info is not None:
+            sampling_info.update_penalties()
+            model_worker_batch.sampling_info = self.cur_sampling_info = dataclasses.replace(
+                sampling_info, sampling_info_done=threading.Event(), penalizer_orchestrator=None)
         self.input_queue.put((model_worker_batch, self.future_token_ids_ct))
         bs = len(model_worker_batch.seq_lens)
         future_next_token_ids = torch.arange(-(self.future_token_ids_ct + 1),
