@@ -332,6 +332,46 @@ SP_API int sp_top_k_top_p_min_p_renorm(const float* probs, int64_t row_stride, c
                                 const float* top_ps, const float* min_ps, int batch_size, int vocab,
                                 float* out, int64_t out_stride, int32_t* keep_count, void* stream);
 
+/* ---- Log-probabilities of a few tokens per row (additive within ABI 10): replaces the dense passes of
+ *      nn/layers/sampler.py:66-67 (log_softmax of a greedy batch), 116-141 (top_p_normalize + log + clamp of a sampled
+ *      one), 234-263 (get_top_logprobs / get_token_ids_logprobs: topk and gathers over [bs, vocab]) and of
+ *      nn/layers/logits_processor.py:378-460 (the same for prompt positions).
+ * rows: fp32 [num_rows, >= vocab], row_stride elements apart, read only.
+ *   kind 0: logits.         value(t) = log_softmax(row)[t]  (-inf for a -inf logit)
+ *   kind 1: probabilities, as sp_softmax_temperature leaves them.  value(t) = log(p[t] / kept_mass) under the top-p
+ *           filter defined above at sp_top_k_top_p_min_p_* (ranks by (p descending, id ascending), mass as integers
+ *           floor(p * 2^48), NaN and entries <= 0 carry no mass; top_ps NULL = keep everything); a token the filter
+ *           drops, one without mass and every token of a row without mass report finfo(float32).min (-FLT_MAX) -
+ *           what log(renorm).clamp(min = finfo.min) yields.  top_ps is ignored for kind 0.
+ * What is asked for, each part optional, and nothing else is written (no [num_rows, vocab] intermediate):
+ *   - chosen_ids int64 [num_rows] (NULL = none)   -> out_chosen[b] = value(chosen_ids[b]);
+ *   - the first top_ks[b] tokens (int32, 0 = none, clamped to max_top_k; top_ks NULL = max_top_k for every row) of the
+ *     ranking by the INPUT value - logit or probability, not the computed logprob - descending, token id ascending: the
+ *     rule of the filter and of sp_argmax, exact under ties and independent of how a row is split over workgroups
+ *     -> out_top_vals / out_top_ids [num_rows, max_top_k], entries [b, 0 .. top_ks[b]) (at most `vocab` of them);
+ *     max_top_k <= SP_LOGPROBS_MAX_TOP_K, else SP_ERR_INVALID_ARG (the caller keeps its own path for longer lists);
+ *   - listed ids in CSR form, ids_offsets int32 [num_rows + 1] and ids_flat int64 (NULL together = none)
+ *     -> out_ids_vals[i] = value(ids_flat[i]) of the row that lists it, for ids_offsets[0] <= i < ids_offsets[num_rows].
+ * An id outside [0, vocab) in chosen_ids or ids_flat lives in device memory, so it cannot be refused here: it reports
+ * finfo(float32).min and nothing is read for it.
+ * The row is streamed once (running maximum and sum of exponentials, or the integer mass, and the top candidates kept
+ * as a sorted list per wave - no sort, no histogram); few rows are cut into up to 32 slices over as many workgroups and
+ * merged per row by a second launch.  That is the whole cost of kind 0 and of a kind-1 row whose mass is within its top_p.
+ * A kind-1 row whose mass exceeds its top_p is NOT done in one pass: the merge launch repeats the filter's radix descent
+ * on it (three more passes over the row, out of L2 where it still is there), and each asked token that sits on a partly
+ * kept pivot value costs one more scan up to its id.
+ * workspace: sp_logprobs_workspace_bytes(num_rows, vocab, max_top_k) bytes, 8-byte aligned (SP_ERR_WORKSPACE if
+ * workspace_bytes is smaller).  SP_ERR_INVALID_ARG before any launch: NULL rows / workspace, NULL output of a part that
+ * is asked for, ids_offsets without ids_flat or the reverse, negative sizes, vocab <= 0, kind not 0 / 1, row_stride <
+ * vocab, max_top_k outside [0, SP_LOGPROBS_MAX_TOP_K].  num_rows == 0 is SP_OK and launches nothing (the parameter is
+ * not called batch_size for the reason given at sp_penalty_reset below; prompt rows are not a batch anyway).       */
+#define SP_LOGPROBS_MAX_TOP_K 32
+SP_API size_t sp_logprobs_workspace_bytes(int num_rows, int vocab, int max_top_k);
+SP_API int sp_logprobs(const float* rows, int64_t row_stride, int kind, const float* top_ps,
+                const int64_t* chosen_ids, const int32_t* top_ks, int max_top_k, const int32_t* ids_offsets,
+                const int64_t* ids_flat, int num_rows, int vocab, float* out_chosen, float* out_top_vals,
+                int32_t* out_top_ids, float* out_ids_vals, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Sampling penalties and grammar vocab masks (additive within ABI 10): replaces
  *      SamplingBatchInfo.apply_logits_bias (sampling/sampling_batch_info.py:324-344) and the dense per-penalizer
  *      tensors behind it (sampling/penaltylib/penalizers/), and the grammar back-ends' apply_vocab_mask

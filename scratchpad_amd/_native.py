@@ -88,6 +88,8 @@ SIGNATURES = {
     "sp_softmax_temperature": (_i32, [_vp, _i64, _vp, _i32, _i32, _vp]),
     "sp_top_k_top_p_min_p_sample": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "sp_top_k_top_p_min_p_renorm": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "sp_logprobs_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "sp_logprobs": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sp_penalty_reset": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "sp_penalty_cumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "sp_penalty_apply": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
@@ -641,6 +643,92 @@ def top_k_top_p_min_p_renorm(probs: torch.Tensor, top_ks: Optional[torch.Tensor]
                                               bs, vocab, out.data_ptr(), out.stride(0), _ptr(cnt), _stream()),
            "sp_top_k_top_p_min_p_renorm")
     return (out, cnt) if return_keep_count else out
+
+
+# --------------------------------------------------------------------------- log-probabilities
+LOGPROBS_MAX_TOP_K = 32       # SP_LOGPROBS_MAX_TOP_K of the header: longer top lists keep the torch path
+LOGPROB_CHUNK_ROWS = 512      # prompt rows projected and reduced at a time (LogitsProcessor); SP_LOGPROB_CHUNK_ROWS
+# launches of sp_logprobs made through this module (tests: a logprob batch on the device path raises it, a batch that
+# asks for none leaves it where it was)
+LOGPROB_LAUNCHES = {"logprobs": 0}
+
+
+def device_logprobs_on() -> bool:
+    """SP_DEVICE_LOGPROBS=0 restores the dense torch passes (log_softmax / renormalise + log, topk, gathers) in
+    Sampler.forward and LogitsProcessor.  Read per call, so one process can run both paths side by side."""
+    return os.environ.get("SP_DEVICE_LOGPROBS", "1") != "0"
+
+
+def logprob_chunk_rows() -> int:
+    return max(1, int(os.environ.get("SP_LOGPROB_CHUNK_ROWS", "") or LOGPROB_CHUNK_ROWS))
+
+
+class LogprobResult:
+    """What one sp_logprobs launch left on the device, in ONE buffer of 4-byte words
+    [chosen n | top values n x K | top ids n x K (int32) | listed-id values]; ``chosen`` is a device view of it and
+    ``lists()`` brings the rest to the host in one copy."""
+
+    def __init__(self, packed: torch.Tensor, n: int, K: int, top_ks, offsets, has_chosen: bool):
+        self._packed, self._n, self._K, self._top_ks, self._offsets = packed, n, K, top_ks, offsets
+        self.chosen = packed[:n] if has_chosen else None
+
+    def lists(self):
+        """(top values, top ids, listed-id values): per row, lists of the lengths that were asked for."""
+        n, K, offs = self._n, self._K, self._offsets
+        if K == 0 and offs[-1] == 0:
+            return [[] for _ in range(n)], [[] for _ in range(n)], [[] for _ in range(n)]
+        host = self._packed.cpu()
+        vals = host[n:n + n * K].view(n, K).tolist() if K else [[]] * n
+        ids = host[n + n * K:n + 2 * n * K].view(torch.int32).view(n, K).tolist() if K else [[]] * n
+        flat = host[n + 2 * n * K:].tolist()
+        return ([vals[i][:self._top_ks[i]] for i in range(n)], [ids[i][:self._top_ks[i]] for i in range(n)],
+                [flat[offs[i]:offs[i + 1]] for i in range(n)])
+
+
+def logprobs(rows: torch.Tensor, kind: int, chosen_ids: Optional[torch.Tensor] = None, top_ks=None, token_ids=None,
+             top_ps: Optional[torch.Tensor] = None, vocab: Optional[int] = None) -> LogprobResult:
+    """sp_logprobs on fp32 rows [n, >= vocab]: kind 0 = logits (log_softmax), kind 1 = probabilities under the top-p
+    filter of ``top_ps`` (dropped tokens: finfo.min).  ``chosen_ids`` int64 [n] on the device; ``top_ks`` a host list of
+    n ints (each at most LOGPROBS_MAX_TOP_K); ``token_ids`` a host list of n id lists (None = none for that row)."""
+    _gpu(rows, chosen_ids, top_ps)
+    rows = _prob_rows(rows, "logprobs")
+    if rows.dtype != torch.float32:
+        raise RuntimeError("logprobs: fp32 rows expected (LogitsProcessor returns fp32)")
+    n = rows.shape[0]
+    vocab = rows.shape[1] if vocab is None else int(vocab)
+    if not 0 < vocab <= rows.shape[1]:
+        raise RuntimeError("logprobs: vocab out of range")
+    dev = rows.device
+    top_ks = [max(int(k), 0) for k in top_ks] if top_ks else [0] * n
+    token_ids = [list(t) if t is not None else [] for t in token_ids] if token_ids else [[] for _ in range(n)]
+    if len(top_ks) != n or len(token_ids) != n:
+        raise RuntimeError(f"logprobs: {n} rows, {len(top_ks)} top_ks, {len(token_ids)} id lists")
+    K = max(top_ks, default=0)
+    if K > LOGPROBS_MAX_TOP_K:
+        raise RuntimeError(f"logprobs: top {K} is above the kernel's {LOGPROBS_MAX_TOP_K} (the caller keeps the torch path)")
+    offsets = [0]
+    for t in token_ids:
+        offsets.append(offsets[-1] + len(t))
+    total = offsets[-1]
+    chosen = _opt(chosen_ids, torch.int64, n, "chosen_ids")
+    ps = _opt(top_ps, torch.float32, n, "top_ps") if kind == 1 else None
+    meta = torch.tensor(top_ks + offsets, dtype=torch.int32).to(dev, non_blocking=True) if n else None
+    flat = (torch.tensor([i for t in token_ids for i in t], dtype=torch.int64).to(dev, non_blocking=True)
+            if total else None)
+    packed = torch.empty(n + 2 * n * K + total, dtype=torch.float32, device=dev)
+    lib = load()
+    ws_bytes = int(lib.sp_logprobs_workspace_bytes(n, vocab, K))
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    base, w = packed.data_ptr(), 4
+    _check(lib.sp_logprobs(rows.data_ptr(), rows.stride(0), int(kind), _ptr(ps), _ptr(chosen),
+                           meta.data_ptr() if n and K else None, K,
+                           meta.data_ptr() + w * n if n and total else None, _ptr(flat), n, vocab,
+                           base if chosen is not None else None, base + w * n if K else None,
+                           base + w * (n + n * K) if K else None, base + w * (n + 2 * n * K) if total else None,
+                           ws.data_ptr(), ws_bytes, _stream()), "sp_logprobs")
+    if n:
+        LOGPROB_LAUNCHES["logprobs"] += 1
+    return LogprobResult(packed, n, K, top_ks, offsets, chosen is not None)
 
 
 # --------------------------------------------------------------------------- penalties / vocab masks

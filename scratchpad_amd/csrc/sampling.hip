@@ -414,6 +414,302 @@ __global__ __launch_bounds__(kSampThreads) void softmax_temperature_kernel(float
   for (int i = tid; i < vocab; i += kSampThreads) row[i] = expf(row[i] / t - mx) * inv;
 }
 
+// ---- log-probabilities of a few tokens per row (sp_logprobs) ---------------------------------
+// Replaces nn/layers/sampler.py:66-67, 116-141, 234-263 and nn/layers/logits_processor.py:378-460: a log_softmax (or
+// renormalise + log + clamp) over [rows, vocab], a topk over the result and gathers out of it, for a few dozen numbers
+// per row.  Two launches, no [rows, vocab] intermediate:
+//   partial: workgroup (row, split) streams its slice of the row ONCE with 16-byte loads and keeps, per lane, the
+//            running (max, sum-exp) of a logit row or the integer mass floor(p * 2^48) of a probability row, and per
+//            WAVE the slice's best `top_k` entries as a sorted list held one entry per lane: a candidate above the
+//            list's last entry is inserted with one ballot and one lane shift, everything else costs one compare.
+//            Entries are ranked by the 64-bit key (value bits made monotone, ~token id): value descending, id
+//            ascending, all keys distinct - so the result does not depend on how the row was cut.
+//   merge:   one workgroup per row folds the splits' statistics and lists, finds the top-p cut of a probability row
+//            whose mass exceeds its top_p with select_cut() above (the row is then re-read from L2, as the sampler
+//            does), and writes the asked values only.
+constexpr int kLogprobMaxTopK = 32;      // = SP_LOGPROBS_MAX_TOP_K
+constexpr int kLogprobMaxSplits = 32;
+constexpr int kLogprobMinSlice = 4096;   // one 16-byte load per thread
+constexpr int kLogprobGroups = 256;      // workgroups wanted per launch: one per compute unit
+constexpr float kLogprobFloor = -3.402823466e+38f;   // finfo(float32).min
+
+inline int logprob_splits(int num_rows, int vocab) {
+  int s = kLogprobGroups / (num_rows > 0 ? num_rows : 1);
+  if (s > vocab / kLogprobMinSlice) s = vocab / kLogprobMinSlice;
+  if (s > kLogprobMaxSplits) s = kLogprobMaxSplits;
+  return s > 1 ? s : 1;
+}
+inline int logprob_slice(int vocab, int splits) { return (((vocab + splits - 1) / splits) + 3) & ~3; }
+
+struct LogprobStat {   // of one (row, split)
+  float mx, sum;       // kind 0: running maximum and sum of exp(x - mx)
+  uint64_t mass;       // kind 1: sum of floor(p * 2^48)
+};
+
+struct LogprobArgs {
+  const float* rows;
+  int64_t row_stride;
+  int kind, vocab, splits, slice, max_top_k;
+  const float* top_ps;
+  const int64_t* chosen_ids;
+  const int32_t* top_ks;
+  const int32_t* ids_offsets;
+  const int64_t* ids_flat;
+  float* out_chosen;
+  float* out_top_vals;
+  int32_t* out_top_ids;
+  float* out_ids_vals;
+  LogprobStat* stats;   // [num_rows, splits]
+  uint64_t* keys;       // [num_rows, splits, max_top_k]
+};
+
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
+  const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+// larger key = ranked earlier: value descending (-0 counts as +0), then token id ascending; never 0
+__device__ __forceinline__ uint64_t rank_key(float v, int id) {
+  uint32_t u = as_u32(v + 0.f);
+  u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
+  return ((uint64_t)u << 32) | (0xffffffffu - (uint32_t)id);
+}
+__device__ __forceinline__ float key_value(uint64_t k) {
+  uint32_t u = (uint32_t)(k >> 32);
+  u ^= (u >> 31) ? 0x80000000u : 0xffffffffu;
+  return as_f32(u);
+}
+__device__ __forceinline__ int key_id(uint64_t k) { return (int)(0xffffffffu - (uint32_t)k); }
+
+// The wave's list: lane l holds its l-th best key so far (0 = none yet), `thr` = the entry of lane k - 1.  Offers one
+// candidate per lane (0 = none).  Wave-uniform control flow: call with all 64 lanes.
+__device__ __forceinline__ void topk_offer(uint64_t& mine, uint64_t& thr, uint64_t c, int k, int lane) {
+  uint64_t m = __ballot(c > thr);
+  while (m) {
+    const int src = __ffsll((unsigned long long)m) - 1;
+    m &= m - 1;
+    const uint64_t cand = shfl_u64(c, src);
+    if (cand <= thr) continue;                     // the list has moved on since the ballot
+    const int pos = __popcll(__ballot(mine > cand));   // sorted: the lanes above the candidate are a prefix
+    const uint64_t up = shfl_up_u64(mine, 1);
+    if (lane > pos) mine = up;
+    else if (lane == pos) mine = cand;
+    thr = shfl_u64(mine, k - 1);
+  }
+}
+
+// (mx, sum) <- (mx, sum) + (omx, osum); a side that has seen nothing finite is (-inf, 0)
+__device__ __forceinline__ void lse_merge(float& mx, float& sum, float omx, float osum) {
+  const float nm = fmaxf(mx, omx);
+  if (nm > -INFINITY) {
+    sum = sum * expf(mx - nm) + osum * expf(omx - nm);
+    mx = nm;
+  }
+}
+
+struct LogprobLane {
+  float mx = -INFINITY, sum = 0.f;
+  uint64_t mass = 0;
+};
+
+__device__ __forceinline__ void logprob_stat4(LogprobLane& st, int kind, const float* f, int n) {
+  if (kind == 0) {
+    float nm = st.mx;
+    for (int e = 0; e < n; ++e) nm = fmaxf(nm, f[e]);
+    if (nm > -INFINITY) {
+      float s = st.sum * expf(st.mx - nm);
+      for (int e = 0; e < n; ++e) s += expf(f[e] - nm);
+      st.sum = s;
+      st.mx = nm;
+    }
+  } else {
+    for (int e = 0; e < n; ++e) st.mass += fx_of_bits(prob_bits(f[e]));
+  }
+}
+
+// fold the 64 lanes' statistics; every lane returns the total
+__device__ __forceinline__ void logprob_wave_fold(LogprobLane& st) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lse_merge(st.mx, st.sum, __shfl_xor(st.mx, off, 64), __shfl_xor(st.sum, off, 64));
+    st.mass += shfl_xor_u64(st.mass, off);
+  }
+}
+
+__global__ __launch_bounds__(kSampThreads) void logprob_partial_kernel(LogprobArgs a) {
+  __shared__ uint64_t s_keys[kSampWaves][kLogprobMaxTopK];
+  __shared__ LogprobStat s_stat[kSampWaves];
+  const int b = blockIdx.x, split = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lo = min(split * a.slice, a.vocab), hi = min(lo + a.slice, a.vocab), n = hi - lo;
+  const float* __restrict__ p = a.rows + (int64_t)b * a.row_stride + lo;
+  const int K = a.max_top_k;
+  LogprobLane st;
+  uint64_t mine = 0, thr = 0;
+
+  // [0, head): up to the first 16-byte boundary; then nvec vectors; then [tail0, n)
+  const int head = min(n, (int)(((16 - ((uintptr_t)p & 15)) & 15) >> 2));
+  const int nvec = (n - head) >> 2, tail0 = head + 4 * nvec;
+  const int iters = (nvec + kSampThreads - 1) / kSampThreads;
+#pragma unroll 1
+  for (int it = 0; it < iters; ++it) {
+    const int i = it * kSampThreads + tid;
+    const bool ok = i < nvec;
+    float f[4] = {0.f, 0.f, 0.f, 0.f};
+    if (ok) {
+      unpack16<f32_tag>(ld16(p + head + 4 * i), f);
+      logprob_stat4(st, a.kind, f, 4);
+    }
+    if (K > 0) {
+      const int id0 = lo + head + 4 * i;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) topk_offer(mine, thr, ok ? rank_key(f[e], id0 + e) : 0, K, lane);
+    }
+  }
+  if (wave == 0) {   // the at most 3 + 3 elements beside the vectors: lanes 0..2 and 8..10
+    int i = -1;
+    if (lane < head) i = lane;
+    else if (lane >= 8 && tail0 + (lane - 8) < n) i = tail0 + (lane - 8);
+    float x = 0.f;
+    if (i >= 0) {
+      x = p[i];
+      logprob_stat4(st, a.kind, &x, 1);
+    }
+    if (K > 0) topk_offer(mine, thr, i >= 0 ? rank_key(x, lo + i) : 0, K, lane);
+  }
+
+  logprob_wave_fold(st);
+  if (lane == 0) s_stat[wave] = LogprobStat{st.mx, st.sum, st.mass};
+  if (lane < K) s_keys[wave][lane] = mine;
+  __syncthreads();
+  if (wave != 0) return;
+  LogprobLane all;
+  if (lane < kSampWaves) { all.mx = s_stat[lane].mx; all.sum = s_stat[lane].sum; all.mass = s_stat[lane].mass; }
+  logprob_wave_fold(all);
+  const int64_t slot = (int64_t)b * a.splits + split;
+  if (lane == 0) a.stats[slot] = LogprobStat{all.mx, all.sum, all.mass};
+  if (K > 0) {
+    for (int w = 1; w < kSampWaves; ++w) topk_offer(mine, thr, lane < K ? s_keys[w][lane] : 0, K, lane);
+    if (lane < K) a.keys[slot * K + lane] = mine;
+  }
+}
+
+__global__ __launch_bounds__(kSampThreads) void logprob_merge_kernel(LogprobArgs a) {
+  __shared__ SelectShared sh;
+  __shared__ uint64_t s_top[kLogprobMaxTopK];
+  __shared__ LogprobStat s_all;
+  __shared__ int s_pick, s_pick_t;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* __restrict__ row = a.rows + (int64_t)b * a.row_stride;
+  const int K = a.max_top_k;
+
+  if (wave == 0) {
+    LogprobLane all;
+    if (lane < a.splits) {
+      const LogprobStat s = a.stats[(int64_t)b * a.splits + lane];
+      all.mx = s.mx; all.sum = s.sum; all.mass = s.mass;
+    }
+    logprob_wave_fold(all);
+    if (lane == 0) s_all = LogprobStat{all.mx, all.sum, all.mass};
+    if (K > 0) {
+      uint64_t mine = 0, thr = 0;
+      for (int s = 0; s < a.splits; ++s)
+        topk_offer(mine, thr, lane < K ? a.keys[((int64_t)b * a.splits + s) * K + lane] : 0, K, lane);
+      if (lane < K) s_top[lane] = mine;
+    }
+  }
+  __syncthreads();
+
+  // kind 0: log_softmax(row)[t] = x - lse.  kind 1: log(p / kept mass) under the cut, kLogprobFloor where dropped
+  const double lse = (double)s_all.mx + log((double)s_all.sum);
+  Cut cut{0u, 0xffffffffu, 0u, s_all.mass};
+  uint32_t pivot_count = 0;
+  if (a.kind == 1 && a.top_ps) {
+    const uint64_t top_p_fx = (uint64_t)((double)a.top_ps[b] * kFxOne);
+    if (s_all.mass > top_p_fx) {   // else no token has more than top_p ranked above it: all are kept
+      SelectArgs sa{a.rows, a.row_stride, nullptr, a.top_ps, nullptr, nullptr, a.vocab, nullptr, nullptr, 0, nullptr};
+      cut = select_cut(sa, row, sh, b);
+      pivot_count = sh.sel_cnt;
+      __syncthreads();
+    }
+  }
+  const bool keep_all = cut.ties_kept == 0xffffffffu;
+  const double log_total = cut.total ? log((double)cut.total / kFxOne) : 0.0;
+
+  const int k_row = K > 0 ? (a.top_ks ? min(max(a.top_ks[b], 0), K) : K) : 0;
+  const int ids_lo = a.ids_offsets ? a.ids_offsets[b] : 0;
+  const int n_ids = a.ids_offsets ? max(a.ids_offsets[b + 1] - ids_lo, 0) : 0;
+  const int n_chosen = a.chosen_ids ? 1 : 0;
+  const int nq = n_chosen + k_row + n_ids;
+#pragma unroll 1
+  for (int base = 0; base < nq; base += kSampThreads) {
+    const int q = base + tid;
+    float* dst = nullptr;
+    int64_t t = -1;
+    float x = 0.f;
+    if (q < nq) {
+      if (q < n_chosen) {
+        dst = a.out_chosen + b;
+        t = a.chosen_ids[b];
+      } else if (q < n_chosen + k_row) {
+        const int j = q - n_chosen;
+        const uint64_t key = s_top[j];
+        if (key) {               // fewer than k_row tokens in the vocabulary: the rest is not written
+          dst = a.out_top_vals + (int64_t)b * K + j;
+          t = key_id(key);
+          a.out_top_ids[(int64_t)b * K + j] = (int32_t)t;
+        }
+      } else {
+        const int j = q - n_chosen - k_row;
+        dst = a.out_ids_vals + ids_lo + j;
+        t = a.ids_flat[ids_lo + j];
+      }
+    }
+    const bool in_range = dst && t >= 0 && t < a.vocab;
+    if (in_range) x = row[t];
+    float result = kLogprobFloor;   // an id outside the vocabulary, a dropped or massless token
+    bool pending = false;           // a token on the pivot of which only the first ties_kept are kept
+    if (in_range) {
+      if (a.kind == 0) {
+        result = (float)((double)x - lse);
+      } else {
+        const uint32_t bits = prob_bits(x);
+        bool kept = bits && cut.total && (keep_all || bits > cut.pivot);
+        if (bits && cut.total && !keep_all && bits == cut.pivot) {
+          if (cut.ties_kept >= pivot_count) kept = true;
+          else if (cut.ties_kept > 0) pending = true;
+        }
+        if (kept) result = (float)(log((double)as_f32(bits)) - log_total);
+      }
+    }
+    // pending tokens, one at a time: rank among the pivot's ties = ties with a lower id
+    while (true) {
+      if (tid == 0) s_pick = 0x7fffffff;
+      __syncthreads();
+      if (pending) atomicMin(&s_pick, tid);
+      __syncthreads();
+      const int pick = s_pick;
+      if (pick == 0x7fffffff) break;
+      if (tid == pick) s_pick_t = (int)t;
+      __syncthreads();
+      const int upto = s_pick_t;
+      uint32_t before = 0;
+      for (int i = tid; i < upto; i += kSampThreads) before += prob_bits(row[i]) == cut.pivot;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
+      if (lane == 0) sh.red_u32[wave] = before;
+      __syncthreads();
+      if (tid == pick) {
+        before = 0;
+        for (int w = 0; w < kSampWaves; ++w) before += sh.red_u32[w];
+        if (before < cut.ties_kept) result = (float)(log((double)as_f32(cut.pivot)) - log_total);
+        pending = false;
+      }
+      __syncthreads();
+    }
+    if (dst) *dst = result;
+  }
+}
+
 }  // namespace sp
 
 extern "C" int sp_argmax(const void* logits, int64_t row_stride, int batch_size, int vocab, int64_t* out_ids,
@@ -482,6 +778,38 @@ extern "C" int sp_top_k_top_p_min_p_renorm(const float* probs, int64_t row_strid
   SP_CHECK_ARG(probs && out && row_stride >= vocab && out_stride >= vocab);
   sp::SelectArgs a{probs, row_stride, top_ks, top_ps, min_ps, nullptr, vocab, nullptr, out, out_stride, keep_count};
   sp::select_kernel<false><<<dim3(batch_size), sp::kSampThreads, 0, (hipStream_t)stream>>>(a);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+extern "C" size_t sp_logprobs_workspace_bytes(int num_rows, int vocab, int max_top_k) {
+  if (num_rows <= 0 || vocab <= 0 || max_top_k < 0 || max_top_k > sp::kLogprobMaxTopK) return 0;
+  const size_t slots = (size_t)num_rows * sp::logprob_splits(num_rows, vocab);
+  return slots * (sizeof(sp::LogprobStat) + sizeof(uint64_t) * (size_t)max_top_k);
+}
+
+extern "C" int sp_logprobs(const float* rows, int64_t row_stride, int kind, const float* top_ps,
+                           const int64_t* chosen_ids, const int32_t* top_ks, int max_top_k,
+                           const int32_t* ids_offsets, const int64_t* ids_flat, int num_rows, int vocab,
+                           float* out_chosen, float* out_top_vals, int32_t* out_top_ids, float* out_ids_vals,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  SP_CHECK_ARG(num_rows >= 0 && vocab > 0 && (kind == 0 || kind == 1));
+  SP_CHECK_ARG(max_top_k >= 0 && max_top_k <= sp::kLogprobMaxTopK);
+  if (num_rows == 0) return SP_OK;
+  SP_CHECK_ARG(rows && workspace && row_stride >= vocab);
+  SP_CHECK_ARG(!chosen_ids || out_chosen);
+  SP_CHECK_ARG(max_top_k == 0 || (out_top_vals && out_top_ids));
+  SP_CHECK_ARG((ids_offsets == nullptr) == (ids_flat == nullptr) && (!ids_offsets || out_ids_vals));
+  if (workspace_bytes < sp_logprobs_workspace_bytes(num_rows, vocab, max_top_k)) return SP_ERR_WORKSPACE;
+  const int splits = sp::logprob_splits(num_rows, vocab);
+  sp::LogprobStat* stats = (sp::LogprobStat*)workspace;
+  sp::LogprobArgs a{rows, row_stride, kind, vocab, splits, sp::logprob_slice(vocab, splits), max_top_k,
+                    kind == 1 ? top_ps : nullptr, chosen_ids, top_ks, ids_offsets, ids_flat,
+                    out_chosen, out_top_vals, out_top_ids, out_ids_vals,
+                    stats, (uint64_t*)(stats + (size_t)num_rows * splits)};
+  sp::logprob_partial_kernel<<<dim3(num_rows, splits), sp::kSampThreads, 0, (hipStream_t)stream>>>(a);
+  SP_LAUNCH_CHECK();
+  sp::logprob_merge_kernel<<<dim3(num_rows), sp::kSampThreads, 0, (hipStream_t)stream>>>(a);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

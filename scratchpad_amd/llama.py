@@ -10,6 +10,7 @@ RowParallelLinear + all-reduce (1033-1155), VocabParallelEmbedding + all-reduce
 (nn/layers/logits_processor.py:179-203, 344-376).  GEMMs stay on torch (hipBLASLt/rocBLAS):
 they are outside the path this package re-kernels.
 """
+import bisect
 from typing import Any, Dict, Iterable, Optional, Tuple
 
 import torch
@@ -286,6 +287,82 @@ class LogitsProcessor(nn.Module):
             logits = tensor_model_parallel_all_gather(logits)
         return logits[:, : self.config.vocab_size].float()
 
+    def _input_logprobs_chunked(self, pruned, lm_head, fb, spans, sample_idx, input_idx, pruned_lens):
+        """The kept rows in chunks of at most SP_LOGPROB_CHUNK_ROWS: project a chunk (the library GEMM), hand its
+        sampled rows to next_token_logits, and reduce it with sp_logprobs (kind 0) to the input-token logprob, the
+        owning request's top-k and its listed ids.  No [kept rows, vocab] matrix exists at any time; a chunk's fp32
+        logits are released before the next is projected."""
+        dev, vocab, R = pruned.device, self.config.vocab_size, pruned.shape[0]
+        tops = fb.top_logprobs_nums or [0] * len(spans)
+        id_lists = fb.token_ids_logprobs or [None] * len(spans)
+        want_top = any(k > 0 for k in tops)
+        want_ids = any(t is not None for t in id_lists)
+        # per kept row: what it asks for (a row that is only sampled asks for nothing)
+        row_top, row_ids, row_req, r = [0] * R, [None] * R, [0] * R, 0
+        for i, ((a, b), n) in enumerate(zip(spans, pruned_lens)):
+            for j in range(b - a):
+                row_req[r + j] = i
+                if j < n:
+                    row_top[r + j], row_ids[r + j] = tops[i], id_lists[i]
+            r += b - a
+        input_rows = torch.tensor(input_idx, device=dev, dtype=torch.int64)
+        chosen = torch.zeros(R, dtype=torch.int64, device=dev)
+        chosen[input_rows] = fb.extend_input_logprob_token_ids_gpu.to(torch.int64)
+        info = fb.sampling_info
+        temps = None
+        if fb.temp_scaled_logprobs and info is not None:
+            # logits_processor.py:292-301, 441-442: the input logprobs (not the sampled logits) see the temperature
+            temps = info.temperatures.view(-1)[torch.tensor(row_req, device=dev)].view(-1, 1)
+        next_logits = torch.empty((len(sample_idx), vocab), dtype=torch.float32, device=dev)
+        sample_rows = torch.tensor(sample_idx, device=dev, dtype=torch.int64)     # ascending: one per request
+        token_logprobs = torch.empty(R, dtype=torch.float32, device=dev)
+        top_val, top_idx, ids_val = [], [], []
+        C = _native.logprob_chunk_rows()
+        for c0 in range(0, R, C):
+            c1 = min(c0 + C, R)
+            logits = self._full_logits(pruned[c0:c1], lm_head)
+            lo, hi = bisect.bisect_left(sample_idx, c0), bisect.bisect_left(sample_idx, c1)
+            if hi > lo:                                       # the sampled rows that fall into this chunk
+                next_logits[lo:hi] = logits[sample_rows[lo:hi] - c0]
+            if temps is not None:
+                logits = logits / temps[c0:c1]
+            res = _native.logprobs(logits, 0, chosen[c0:c1], row_top[c0:c1] if want_top else None,
+                                   row_ids[c0:c1] if want_ids else None, vocab=vocab)
+            token_logprobs[c0:c1] = res.chosen
+            if want_top or want_ids:
+                tv, ti, iv = res.lists()
+                top_val += tv
+                top_idx += ti
+                ids_val += iv
+            del logits, res
+        out = LogitsProcessorOutput(next_token_logits=next_logits, vocab_size=vocab)
+        first = [a for a, _ in self._kept_row_starts(spans)]
+        if want_top:
+            # get_top_logprobs, logits_processor.py:378-405
+            out.input_top_logprobs_val = [[top_val[f + j] for j in range(max(n, 0))] for f, n in zip(first, pruned_lens)]
+            out.input_top_logprobs_idx = [[top_idx[f + j] for j in range(max(n, 0))] for f, n in zip(first, pruned_lens)]
+        if want_ids:
+            # get_token_ids_logprobs, 407-430
+            out.input_token_ids_logprobs_val, out.input_token_ids_logprobs_idx = [], []
+            for f, n, ids in zip(first, pruned_lens, id_lists):
+                if n <= 0 or ids is None:
+                    out.input_token_ids_logprobs_val.append([])
+                    out.input_token_ids_logprobs_idx.append([])
+                    continue
+                out.input_token_ids_logprobs_val.append([ids_val[f + j] for j in range(n)])
+                out.input_token_ids_logprobs_idx.append([ids for _ in range(n)])
+        out.input_token_logprobs = token_logprobs[input_rows]
+        return out
+
+    @staticmethod
+    def _kept_row_starts(spans):
+        """(first kept row, one past the last) of every request among the rows input_logprob_plan keeps"""
+        out, r = [], 0
+        for a, b in spans:
+            out.append((r, r + b - a))
+            r += b - a
+        return out
+
     def forward(self, input_ids, hidden_states, lm_head, forward_batch: ForwardBatch):
         fb = forward_batch
         want_input = (fb.forward_mode.is_extend() and fb.return_logprob and fb.extend_logprob_start_lens_cpu is not None
@@ -303,6 +380,15 @@ class LogitsProcessor(nn.Module):
                                                                             fb.extend_logprob_start_lens_cpu)
         dev = hidden_states.device
         pruned = torch.cat([hidden_states[a:b] for a, b in spans])
+        info = fb.sampling_info
+        top_p_normalized = (fb.top_p_normalized_logprobs and info is not None
+                            and bool((info.top_ps != 1.0).any()))
+        # The chunked device path needs device rows (host tensors keep the dense passes, as every host-side use of
+        # this module does) and is taken at TP = 1 only: under TP > 1 it would issue one all-gather per chunk instead
+        # of one per step, which has not been run on a multi-GPU machine yet.
+        if (_native.device_logprobs_on() and pruned.is_cuda and not top_p_normalized
+                and not self.do_tensor_parallel_all_gather and max(fb.top_logprobs_nums or [0]) <= _native.LOGPROBS_MAX_TOP_K):
+            return self._input_logprobs_chunked(pruned, lm_head, fb, spans, sample_idx, input_idx, pruned_lens)
         logits = self._full_logits(pruned, lm_head)
         out = LogitsProcessorOutput(next_token_logits=logits[torch.tensor(sample_idx, device=dev, dtype=torch.int64)],
                                     vocab_size=self.config.vocab_size)

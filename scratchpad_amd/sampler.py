@@ -366,10 +366,16 @@ class Sampler(nn.Module):
                   else logits_output.next_token_logits)
         if self.use_nan_detection and torch.any(torch.isnan(logits)):
             logits = torch.where(torch.isnan(logits), torch.full_like(logits, -1e5), logits)
-        logprobs = None
+        # return_logprob: one sp_logprobs launch over the rows the sampler has just read and one packed copy to the
+        # host; SP_DEVICE_LOGPROBS=0 and top lists beyond the kernel's cap keep the dense torch passes
+        on_device = (return_logprob and _native.device_logprobs_on()
+                     and max(top_logprobs_nums or [0]) <= _native.LOGPROBS_MAX_TOP_K)
+        logprobs = result = None
         if sampling_info.is_all_greedy:
             ids = _native.argmax(logits)
-            if return_logprob:
+            if on_device:
+                result = _native.logprobs(logits, 0, ids, top_logprobs_nums, token_ids_logprobs)
+            elif return_logprob:
                 logprobs = torch.nn.functional.log_softmax(logits, dim=-1)
         else:
             probs = _native.softmax_temperature_(logits, sampling_info.temperatures)
@@ -378,14 +384,29 @@ class Sampler(nn.Module):
             ids = _native.top_k_top_p_min_p_sample(
                 probs, sampling_info.top_ks, sampling_info.top_ps,
                 sampling_info.min_ps if sampling_info.need_min_p_sampling else None, uniform)
-            if return_logprob:
+            if on_device:
+                result = _native.logprobs(probs, 1, ids, top_logprobs_nums, token_ids_logprobs,
+                                          top_ps=sampling_info.top_ps)
+            elif return_logprob:
                 logprobs = torch.log(top_p_normalize_probs(probs, sampling_info.top_ps)).clamp(
                     min=torch.finfo(probs.dtype).min)
-        if return_logprob:
-            if top_logprobs_nums and any(x > 0 for x in top_logprobs_nums):
+        want_top = bool(top_logprobs_nums) and any(x > 0 for x in top_logprobs_nums)
+        want_ids = bool(token_ids_logprobs) and any(x is not None for x in token_ids_logprobs)
+        if result is not None:
+            if want_top or want_ids:
+                top_val, top_idx, ids_val = result.lists()
+                if want_top:
+                    logits_output.next_token_top_logprobs_val, logits_output.next_token_top_logprobs_idx = top_val, top_idx
+                if want_ids:
+                    logits_output.next_token_token_ids_logprobs_val = ids_val
+                    logits_output.next_token_token_ids_logprobs_idx = [x if x is not None else []
+                                                                       for x in token_ids_logprobs]
+            logits_output.next_token_logprobs = result.chosen
+        elif return_logprob:
+            if want_top:
                 (logits_output.next_token_top_logprobs_val,
                  logits_output.next_token_top_logprobs_idx) = get_top_logprobs(logprobs, top_logprobs_nums)
-            if token_ids_logprobs and any(x is not None for x in token_ids_logprobs):
+            if want_ids:
                 (logits_output.next_token_token_ids_logprobs_val,
                  logits_output.next_token_token_ids_logprobs_idx) = get_token_ids_logprobs(logprobs, token_ids_logprobs)
             logits_output.next_token_logprobs = logprobs[

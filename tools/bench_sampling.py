@@ -1,5 +1,10 @@
 #!/usr/bin/env python3
-"""Time the sampler kernels at the headline shape (bs=256, vocab=128256, fp32)."""
+"""Time the sampler kernels at the headline shape (bs=256, vocab=128256, fp32).
+
+``bench_sampling.py [bs]``: the kernels one by one.  ``bench_sampling.py logprobs``: Sampler.forward with
+return_logprob (top 20 and five listed ids per row) at bs 256 and bs 8, greedy and sampling, on the device path
+(sp_logprobs) and under SP_DEVICE_LOGPROBS=0 (the dense torch passes) in one process.  These are end-to-end times of
+Sampler.forward - the copy that restores the logits, the launches, the host-side lists and their copy - not kernel times."""
 import os
 import sys
 
@@ -22,7 +27,45 @@ def timeit(fn, n=20):
     return e0.elapsed_time(e1) / n * 1e3
 
 
+def logprob_rows():
+    from scratchpad_amd.llama import LogitsProcessorOutput
+    from scratchpad_amd.sampler import Sampler, SamplingBatchInfo, SamplingParams
+    vocab = 128256
+    sampler = Sampler()
+    for bs in (256, 8):
+        g = torch.Generator(device="cuda").manual_seed(bs)
+        logits = (torch.randn(bs, vocab, device="cuda", generator=g) * 3).to(torch.bfloat16).float()
+        scratch = torch.empty_like(logits)
+        u = torch.rand(bs, device="cuda", generator=g)
+        nums = [20] * bs
+        asked = [[(7 * b + j * 1009) % vocab for j in range(5)] for b in range(bs)]
+        for name, params in (("greedy", SamplingParams(temperature=0.0)),
+                             ("sampling", SamplingParams(temperature=0.8, top_p=0.9, top_k=50))):
+            info = SamplingBatchInfo.from_params([params] * bs, vocab, "cuda")
+
+            def step(logprob):
+                scratch.copy_(logits)          # the sampling path softmaxes in place (the copy is in every figure)
+                out = LogitsProcessorOutput(next_token_logits=scratch)
+                if logprob:
+                    sampler(out, info, return_logprob=True, top_logprobs_nums=nums, token_ids_logprobs=asked, uniform=u)
+                else:
+                    sampler(out, info, uniform=u)
+            figures, saved = {}, os.environ.get("SP_DEVICE_LOGPROBS")
+            for switch in ("1", "0"):
+                os.environ["SP_DEVICE_LOGPROBS"] = switch
+                figures[switch] = timeit(lambda: step(True), 30)
+            if saved is None:
+                os.environ.pop("SP_DEVICE_LOGPROBS")
+            else:
+                os.environ["SP_DEVICE_LOGPROBS"] = saved
+            base = timeit(lambda: step(False), 30)
+            print(f"Sampler.forward {name:8s} bs {bs:3d} x {vocab}, top 20 + 5 ids: device {figures['1']:9.1f} us   "
+                  f"torch (SP_DEVICE_LOGPROBS=0) {figures['0']:9.1f} us   without logprobs {base:9.1f} us")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "logprobs":
+        return logprob_rows()
     bs = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     vocab = 128256
     g = torch.Generator(device="cuda").manual_seed(0)
