@@ -100,6 +100,26 @@ SP_API int sp_rotary_embedding(const int64_t* positions, void* q, void* k, const
                         const int64_t* out_cache_loc, int64_t kv_buffer_stride, int dtype,
                         void* stream);
 
+/* ---- Per-head RMSNorm of q and k + rotary embedding (+ fused KV store) in ONE launch: the attention prologue of
+ *      Qwen3 (nn/models/qwen/qwen3.py:114-123 `_apply_qk_norm`, then rotary_emb, then set_kv_buffer).
+ * In place on q and k.  Every [head_size] row of q is normalised with q_norm_weight, every row of k with
+ * k_norm_weight (both [head_size] in `dtype`) exactly as sp_rmsnorm does it with hidden = head_size -
+ * rs = 1/sqrtf(mean(x^2) + eps) in fp32, n = round(round(x * rs) * w) - and sp_rotary_embedding's rotation is then
+ * applied to n (the normed tail beyond rotary_dim is kept).  With k_buffer / v_buffer the normed and rotated k rows
+ * and the untouched v rows are scattered to the pool as sp_rotary_embedding's fused store does; v is never written.
+ * The result is BIT-IDENTICAL to sp_rmsnorm on the [T*Hq, head_size] rows of q, sp_rmsnorm on the [T*Hkv, head_size]
+ * rows of k, then sp_rotary_embedding with the same store arguments.
+ * Built for: head_size in {64, 128, 256}; rotary_dim = head_size or head_size / 2 (neox), a multiple of 16 bytes
+ * (GPT-J); 16-byte aligned pointers and row strides.  Anything else returns SP_ERR_UNSUPPORTED before any launch:
+ * issue the three calls above instead.  Refusals (SP_ERR_INVALID_ARG) are those of sp_rotary_embedding, with both
+ * weights required.                                                                                              */
+SP_API int sp_qk_norm_rotary(const int64_t* positions, void* q, void* k, const void* q_norm_weight,
+                      const void* k_norm_weight, float eps, const void* cos_sin_cache, int64_t num_tokens,
+                      int num_q_heads, int num_kv_heads, int head_size, int rotary_dim, int64_t q_stride,
+                      int64_t k_stride, int is_neox, const void* v, int64_t v_stride, void* k_buffer,
+                      void* v_buffer, const int64_t* out_cache_loc, int64_t kv_buffer_stride, int dtype,
+                      void* stream);
+
 /* ---- KV store: replaces `k_buffer[layer][loc] = cache_k` (MHATokenToKVPool.set_kv_buffer,
  *      memory/pool.py:392-424).  k,v: [T, Hkv, D] (token stride given); buffers [P+1, Hkv, D].  */
 SP_API int sp_kv_store(void* k_buffer, void* v_buffer, const int64_t* loc, const void* k, const void* v,

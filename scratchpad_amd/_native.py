@@ -61,6 +61,8 @@ SIGNATURES = {
     "sp_silu_and_mul": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _i32, _vp]),
     "sp_rotary_embedding": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64,
                                    _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "sp_qk_norm_rotary": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64,
+                                 _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
     "sp_kv_store": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i64,
                            _i64, _i32, _vp]),
     "sp_write_req_to_token": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
@@ -257,6 +259,65 @@ def rotary_embedding(positions: torch.Tensor, query: torch.Tensor, key: torch.Te
         _ptr(value) if fused else None, v_stride, _ptr(k_buffer), _ptr(v_buffer),
         _ptr(out_cache_loc) if fused else None, kv_stride, _dt(query), _stream()),
         "sp_rotary_embedding")
+
+
+# calls of qk_norm_rotary by the path they took: "fused" = one sp_qk_norm_rotary launch, "three_launch" = the library
+# refused the shape (SP_ERR_UNSUPPORTED) and sp_rmsnorm, sp_rmsnorm, sp_rotary_embedding ran instead (tests: the
+# product shapes must count as fused)
+QK_NORM_CALLS = {"fused": 0, "three_launch": 0}
+
+
+def _rmsnorm_heads_(x: torch.Tensor, head_size: int, weight: torch.Tensor, eps: float) -> None:
+    """sp_rmsnorm on the [T * H, head_size] rows of x ([T, H * head_size], row stride free), written back in place"""
+    T = x.shape[0]
+    x.copy_(rmsnorm(x.reshape(-1, head_size), weight, eps).view(T, -1))
+
+
+def qk_norm_rotary(positions: torch.Tensor, query: torch.Tensor, key: torch.Tensor, q_norm_weight: torch.Tensor,
+                   k_norm_weight: torch.Tensor, eps: float, head_size: int, cos_sin_cache: torch.Tensor,
+                   is_neox: bool, value: Optional[torch.Tensor] = None, k_buffer: Optional[torch.Tensor] = None,
+                   v_buffer: Optional[torch.Tensor] = None, out_cache_loc: Optional[torch.Tensor] = None) -> None:
+    """Per-head RMSNorm of query and key (weights [head_size]), then rotary_embedding with the same arguments, in
+    one launch (sp_qk_norm_rotary); in place on query/key like rotary_embedding.  Shapes the kernel is not built for
+    (head_size outside 64 / 128 / 256, a rotary_dim that is neither head_size nor half of it, misaligned views) take
+    rmsnorm + rmsnorm + rotary_embedding here; the bits are the same either way (QK_NORM_CALLS says which ran)."""
+    _gpu(positions, query, key, q_norm_weight, k_norm_weight, cos_sin_cache, value, k_buffer, v_buffer, out_cache_loc)
+    if query.dim() != 2 or key.dim() != 2 or query.stride(-1) != 1 or key.stride(-1) != 1:
+        raise RuntimeError("qk_norm_rotary needs 2-D row-contiguous q and k (in-place op)")
+    if cos_sin_cache.dtype != query.dtype or not cos_sin_cache.is_contiguous():
+        raise RuntimeError("cos_sin_cache must be contiguous and in the activation dtype")
+    if q_norm_weight.shape != (head_size,) or k_norm_weight.shape != (head_size,):
+        raise RuntimeError(f"qk_norm_rotary: the norm weights must be [{head_size}]")
+    wq = (q_norm_weight if q_norm_weight.dtype == query.dtype else q_norm_weight.to(query.dtype)).contiguous()
+    wk = (k_norm_weight if k_norm_weight.dtype == query.dtype else k_norm_weight.to(query.dtype)).contiguous()
+    if positions.dtype != torch.int64:
+        positions = positions.to(torch.int64)
+    positions = positions.contiguous()
+    T = query.shape[0]
+    Hq, Hkv = query.shape[1] // head_size, key.shape[1] // head_size
+    fused = k_buffer is not None
+    kv_stride = v_stride = 0
+    if fused:
+        if value.dim() != 2 or value.stride(-1) != 1:
+            raise RuntimeError("fused KV store needs a 2-D row-contiguous value")
+        if out_cache_loc.dtype != torch.int64:
+            out_cache_loc = out_cache_loc.to(torch.int64)
+        _kv_layout(k_buffer, v_buffer, "qk_norm_rotary (fused KV store)")
+        kv_stride, v_stride = k_buffer.stride(0), value.stride(0)
+    status = load().sp_qk_norm_rotary(
+        positions.data_ptr(), query.data_ptr(), key.data_ptr(), wq.data_ptr(), wk.data_ptr(), float(eps),
+        cos_sin_cache.data_ptr(), T, Hq, Hkv, head_size, cos_sin_cache.shape[1], query.stride(0), key.stride(0),
+        int(is_neox), _ptr(value) if fused else None, v_stride, _ptr(k_buffer), _ptr(v_buffer),
+        _ptr(out_cache_loc) if fused else None, kv_stride, _dt(query), _stream())
+    if status == SP_ERR_UNSUPPORTED:
+        _rmsnorm_heads_(query, head_size, wq, eps)
+        _rmsnorm_heads_(key, head_size, wk, eps)
+        rotary_embedding(positions, query, key, head_size, cos_sin_cache, is_neox, value, k_buffer, v_buffer,
+                         out_cache_loc)
+        QK_NORM_CALLS["three_launch"] += 1
+        return
+    _check(status, "sp_qk_norm_rotary")
+    QK_NORM_CALLS["fused"] += 1
 
 
 def kv_store(k_buffer: torch.Tensor, v_buffer: torch.Tensor, loc: torch.Tensor,

@@ -379,20 +379,30 @@ class HipAttnBackend(AttentionBackend):
         return forward_batch.seq_lens, None
 
     def rotary_and_store(self, rope, positions, q, k, v, layer: RadixAttention,
-                         forward_batch: "ForwardBatch") -> None:
+                         forward_batch: "ForwardBatch", q_norm=None, k_norm=None) -> None:
         """rotary_emb(positions, q, k) + set_kv_buffer(layer, out_cache_loc, k, v) in one launch
-        (rotary_embedding.py:132-164 followed by pool.py:392-424).  q and k are rotated in place."""
+        (rotary_embedding.py:132-164 followed by pool.py:392-424).  q and k are rotated in place.
+        With ``q_norm`` / ``k_norm`` (the per-head RMSNorm modules of a Qwen3 layer, qwen3.py:114-123) every head of q
+        and k is normalised first, in the same launch (sp_qk_norm_rotary)."""
         pool = forward_batch.token_to_kv_pool
         if rope.cos_sin_cache.device != q.device or rope.cos_sin_cache.dtype != q.dtype:
             rope.cos_sin_cache = rope.cos_sin_cache.to(q.device, dtype=q.dtype)
-        if pool.dtype != q.dtype or layer.is_cross_attention:
+        if (q_norm is None) != (k_norm is None):
+            raise RuntimeError("rotary_and_store: q_norm and k_norm go together")
+        # a pool of another dtype (fp8) or a cross-attention layer: the store is the pool's own, behind the rotation
+        fuse_store = pool.dtype == q.dtype and not layer.is_cross_attention
+        kb, vb = pool.get_kv_buffer(layer.layer_id) if fuse_store else (None, None)
+        store = dict(value=v, k_buffer=kb, v_buffer=vb, out_cache_loc=forward_batch.out_cache_loc) if fuse_store else {}
+        if q_norm is not None:
+            _native.qk_norm_rotary(positions, q, k, q_norm.weight.data, k_norm.weight.data, q_norm.variance_epsilon,
+                                   rope.head_size, rope.cos_sin_cache, rope.is_neox_style, **store)
+        elif fuse_store:
+            _native.rotary_embedding(positions, q, k, rope.head_size, rope.cos_sin_cache, rope.is_neox_style, **store)
+        else:
             rope(positions, q, k)
+        if not fuse_store:
             self._store(layer, forward_batch, k.view(-1, layer.tp_k_head_num, layer.qk_head_dim),
                         v.view(-1, layer.tp_v_head_num, layer.v_head_dim), True)
-            return
-        kb, vb = pool.get_kv_buffer(layer.layer_id)
-        _native.rotary_embedding(positions, q, k, rope.head_size, rope.cos_sin_cache, rope.is_neox_style,
-                                 value=v, k_buffer=kb, v_buffer=vb, out_cache_loc=forward_batch.out_cache_loc)
 
     def _kv_scales(self, layer: RadixAttention):
         """flashinfer_backend.py:400-401, 457-458: the layer's float scales, only for a non-"auto"

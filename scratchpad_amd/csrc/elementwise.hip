@@ -298,6 +298,140 @@ __global__ __launch_bounds__(kBlock) void rotary_kernel(RotaryArgs a) {
   }
 }
 
+// ------------------------------------------------- per-head RMSNorm + rotary (+ fused KV store)
+// nn/models/qwen/qwen3.py:114-123 (_apply_qk_norm) followed by rotary_emb and set_kv_buffer, in one launch whose
+// bits are those of rmsnorm_vec_kernel on the [T*H, D] rows of q and of k followed by rotary_kernel.
+//
+// One workgroup per token, L = D / (2 * kVec) lanes per head: lane j of a head holds its 16-byte vectors j (A) and
+// j + L (B = A's neox partner at rotary_dim = D).  rmsnorm_vec_kernel at hidden = D has lane v sum the squares of
+// vector v in element order and folds the lanes with xor offsets 32 ... 1 (wave_sum), then adds three zero waves
+// (block_sum): every add above offset L is an add of exact zeros, the xor-L step is A's partial + B's partial - taken
+// here inside the lane - and the steps below it are the same butterfly over the head's L lanes.  The sum, the mean
+// and rs are therefore the same fp32 numbers; the two products of the norm and the rotation's products and sums keep
+// their rounding points (E::round where the three-launch form stores and reloads a `dtype` value).
+// Norm weights and the cos/sin values depend on the lane's place in its head only: they are loaded once, in front
+// of the loop over the heads this lane group takes.
+struct QkNormArgs {
+  RotaryArgs r;
+  const void* q_weight;
+  const void* k_weight;
+  float eps;
+};
+
+static constexpr int kQkNormMaxBlock = 512;
+
+template <typename Tag, int L>
+__global__ __launch_bounds__(kQkNormMaxBlock) void qk_norm_rotary_kernel(QkNormArgs p) {
+  typedef Elem<Tag> E;
+  constexpr int V = E::kVec;
+  const RotaryArgs& a = p.r;
+  const int64_t t = blockIdx.x;
+  const int64_t pos = a.positions[t];
+  const int half = a.rot / 2;
+  const char* cos_row = (const char*)a.cache + pos * a.rot * E::kBytes;
+  const char* sin_row = cos_row + (int64_t)half * E::kBytes;
+  const bool store = a.k_buffer != nullptr;
+  const int64_t slot = store ? a.loc[t] : 0;
+  char* kdst = store ? (char*)a.k_buffer + slot * a.kv_buffer_stride * E::kBytes : nullptr;
+  const int nheads = a.Hq + a.Hkv;
+  const int j = threadIdx.x & (L - 1), g = threadIdx.x / L, G = blockDim.x / L;
+  const bool full = a.rot == a.head_size;          // else rot = D / 2 (the host admits nothing else)
+  const bool lo = j < L / 2;                        // neox at rot = D / 2: A is x1 (lo) or x2 of its pair
+  const bool rot_b = full;                          // GPT-J: is vector B inside rotary_dim (A always is)
+
+  // c / s: neox - the cos / sin vector this lane's pair uses; GPT-J - [0, V/2) for vector A, [V/2, V) for vector B
+  float c[V], s[V];
+  if (a.is_neox) {
+    const int jj = full ? j : (j & (L / 2 - 1));
+    unpack16<Tag>(ld16(cos_row + (int64_t)jj * 16), c);
+    unpack16<Tag>(ld16(sin_row + (int64_t)jj * 16), s);
+  } else {
+#pragma unroll
+    for (int e = 0; e < V / 2; ++e) {
+      c[e] = E::load(cos_row, j * (V / 2) + e);
+      s[e] = E::load(sin_row, j * (V / 2) + e);
+      c[V / 2 + e] = rot_b ? E::load(cos_row, (j + L) * (V / 2) + e) : 0.f;
+      s[V / 2 + e] = rot_b ? E::load(sin_row, (j + L) * (V / 2) + e) : 0.f;
+    }
+  }
+  u32x4 wqa = {}, wqb = {}, wka = {}, wkb = {};
+  if (a.Hq > 0) {
+    wqa = ld16((const char*)p.q_weight + (int64_t)j * 16);
+    wqb = ld16((const char*)p.q_weight + (int64_t)(j + L) * 16);
+  }
+  if (a.Hkv > 0) {
+    wka = ld16((const char*)p.k_weight + (int64_t)j * 16);
+    wkb = ld16((const char*)p.k_weight + (int64_t)(j + L) * 16);
+  }
+
+  for (int h = g; h < nheads; h += G) {
+    const bool is_k = h >= a.Hq;
+    const int hh = is_k ? h - a.Hq : h;
+    char* base = is_k ? (char*)a.k + (t * a.k_stride + (int64_t)hh * a.head_size) * E::kBytes
+                      : (char*)a.q + (t * a.q_stride + (int64_t)hh * a.head_size) * E::kBytes;
+    float xa[V], xb[V], wa[V], wb[V];
+    unpack16<Tag>(ld16(base + (int64_t)j * 16), xa);
+    unpack16<Tag>(ld16(base + (int64_t)(j + L) * 16), xb);
+    unpack16<Tag>(is_k ? wka : wqa, wa);
+    unpack16<Tag>(is_k ? wkb : wqb, wb);
+    // rmsnorm_vec_kernel's partial sums of vectors j and j + L, then its reduction tree (see above)
+    float ss = 0.f, sb = 0.f;
+#pragma unroll
+    for (int e = 0; e < V; ++e) ss += xa[e] * xa[e];
+#pragma unroll
+    for (int e = 0; e < V; ++e) sb += xb[e] * xb[e];
+    ss += sb;
+#pragma unroll
+    for (int off = L / 2; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    const float mean = ss / (float)a.head_size;
+    const float rs = 1.0f / sqrtf(mean + p.eps);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      xa[e] = E::round(__fmul_rn(E::round(__fmul_rn(xa[e], rs)), wa[e]));
+      xb[e] = E::round(__fmul_rn(E::round(__fmul_rn(xb[e], rs)), wb[e]));
+    }
+    float oa[V], ob[V];
+    if (a.is_neox) {
+      if (full) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) rotate_pair<Tag>(xa[e], xb[e], c[e], s[e], oa[e], ob[e]);
+      } else {
+        // pairs (vector i, vector i + L/2) of the first half of the head: the partner is lane j ^ (L/2)'s vector A
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          const float other = __shfl_xor(xa[e], L / 2, 64);
+          float o1, o2;
+          rotate_pair<Tag>(lo ? xa[e] : other, lo ? other : xa[e], c[e], s[e], o1, o2);
+          oa[e] = lo ? o1 : o2;
+          ob[e] = xb[e];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < V / 2; ++e) {
+        rotate_pair<Tag>(xa[2 * e], xa[2 * e + 1], c[e], s[e], oa[2 * e], oa[2 * e + 1]);
+        float o1, o2;
+        rotate_pair<Tag>(xb[2 * e], xb[2 * e + 1], c[V / 2 + e], s[V / 2 + e], o1, o2);
+        ob[2 * e] = rot_b ? o1 : xb[2 * e];
+        ob[2 * e + 1] = rot_b ? o2 : xb[2 * e + 1];
+      }
+    }
+    const u32x4 pa = pack16<Tag>(oa), pb = pack16<Tag>(ob);
+    st16(base + (int64_t)j * 16, pa);
+    st16(base + (int64_t)(j + L) * 16, pb);
+    if (store && is_k) {
+      char* d = kdst + (int64_t)hh * a.head_size * E::kBytes;
+      st16(d + (int64_t)j * 16, pa);
+      st16(d + (int64_t)(j + L) * 16, pb);
+    }
+  }
+  if (!store) return;
+  char* vdst = (char*)a.v_buffer + slot * a.kv_buffer_stride * E::kBytes;
+  const char* vsrc = (const char*)a.v + t * a.v_stride * E::kBytes;
+  const int n = a.Hkv * a.head_size / V;
+  for (int u = threadIdx.x; u < n; u += blockDim.x) st16(vdst + (int64_t)u * 16, ld16(vsrc + (int64_t)u * 16));
+}
+
 // ----------------------------------------------------------------------------------- KV store
 // memory/pool.py:414-424: buffer[loc[t]] = cache[t].  Rows are Hkv*D contiguous elements.
 template <int BYTES>  // 16 (vector) or the element size (scalar)
@@ -546,6 +680,62 @@ extern "C" int sp_rotary_embedding(const int64_t* positions, void* q, void* k,
   a.kv_buffer_stride = kv_buffer_stride; a.Hq = num_q_heads; a.Hkv = num_kv_heads;
   a.head_size = head_size; a.rot = rotary_dim; a.is_neox = is_neox ? 1 : 0;
   SP_DISPATCH_DTYPE(dtype, return (launch_rotary<Tag>(a, num_tokens, (hipStream_t)stream)));
+}
+
+template <typename Tag>
+static int launch_qk_norm_rotary(const QkNormArgs& p, int64_t T, hipStream_t st) {
+  typedef Elem<Tag> E;
+  constexpr int V = E::kVec;
+  const RotaryArgs& a = p.r;
+  const int D = a.head_size;
+  // the lane layout reproduces rmsnorm_vec_kernel's reduction for a power-of-two number of 16-byte vectors per head
+  if (D != 64 && D != 128 && D != 256) return SP_ERR_UNSUPPORTED;
+  if (a.rot != D && a.rot * 2 != D) return SP_ERR_UNSUPPORTED;
+  bool vec = a.q_stride % V == 0 && a.k_stride % V == 0 && aligned16(a.q) && aligned16(a.k) &&
+             aligned16(a.cache) && aligned16(p.q_weight) && aligned16(p.k_weight);
+  if (a.k_buffer)
+    vec = vec && a.v_stride % V == 0 && a.kv_buffer_stride % V == 0 && aligned16(a.v) &&
+          aligned16(a.k_buffer) && aligned16(a.v_buffer);
+  if (!vec) return SP_ERR_UNSUPPORTED;
+  const int L = D / (2 * V);
+  int threads = ((a.Hq + a.Hkv) * L + 63) / 64 * 64;
+  threads = threads < 64 ? 64 : (threads > kQkNormMaxBlock ? kQkNormMaxBlock : threads);
+#define SP_QKN_LAUNCH(LL) qk_norm_rotary_kernel<Tag, LL><<<dim3((unsigned)T), threads, 0, st>>>(p)
+  switch (L) {
+    case 4: SP_QKN_LAUNCH(4); break;
+    case 8: SP_QKN_LAUNCH(8); break;
+    case 16: SP_QKN_LAUNCH(16); break;
+    case 32: SP_QKN_LAUNCH(32); break;
+    default: return SP_ERR_UNSUPPORTED;
+  }
+#undef SP_QKN_LAUNCH
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+extern "C" int sp_qk_norm_rotary(const int64_t* positions, void* q, void* k, const void* q_norm_weight,
+                                 const void* k_norm_weight, float eps, const void* cos_sin_cache,
+                                 int64_t num_tokens, int num_q_heads, int num_kv_heads, int head_size,
+                                 int rotary_dim, int64_t q_stride, int64_t k_stride, int is_neox,
+                                 const void* v, int64_t v_stride, void* k_buffer, void* v_buffer,
+                                 const int64_t* out_cache_loc, int64_t kv_buffer_stride, int dtype,
+                                 void* stream) {
+  SP_CHECK_ARG(positions && q && k && q_norm_weight && k_norm_weight && cos_sin_cache && num_tokens >= 0);
+  SP_CHECK_ARG(num_q_heads >= 0 && num_kv_heads >= 0 && head_size > 0);
+  SP_CHECK_ARG(rotary_dim > 0 && rotary_dim <= head_size && rotary_dim % 2 == 0);
+  const bool store = k_buffer != nullptr || v_buffer != nullptr;
+  if (store) SP_CHECK_ARG(k_buffer && v_buffer && v && out_cache_loc && kv_buffer_stride > 0);
+  if (dtype != SP_F32 && dtype != SP_F16 && dtype != SP_BF16) return SP_ERR_UNSUPPORTED;
+  QkNormArgs p;
+  RotaryArgs& a = p.r;
+  a.positions = positions; a.q = q; a.k = k; a.v = v; a.cache = cos_sin_cache;
+  a.k_buffer = store ? k_buffer : nullptr; a.v_buffer = store ? v_buffer : nullptr;
+  a.loc = out_cache_loc; a.q_stride = q_stride; a.k_stride = k_stride; a.v_stride = v_stride;
+  a.kv_buffer_stride = kv_buffer_stride; a.Hq = num_q_heads; a.Hkv = num_kv_heads;
+  a.head_size = head_size; a.rot = rotary_dim; a.is_neox = is_neox ? 1 : 0;
+  p.q_weight = q_norm_weight; p.k_weight = k_norm_weight; p.eps = eps;
+  if (num_tokens == 0) return SP_OK;
+  SP_DISPATCH_DTYPE(dtype, return (launch_qk_norm_rotary<Tag>(p, num_tokens, (hipStream_t)stream)));
 }
 
 extern "C" int sp_kv_store(void* k_buffer, void* v_buffer, const int64_t* loc, const void* k,

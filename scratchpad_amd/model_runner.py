@@ -43,6 +43,9 @@ class ModelConfig:
     pad_token_id: Optional[int] = None
     # Mllama: the vision tower's config (MllamaVisionConfig fields); None = text side only
     vision_config: Optional[object] = None
+    # which decoder load_model builds: "llama" (with cross_attention_layers: Mllama) or "qwen3"
+    architecture: str = "llama"
+    attention_bias: bool = False        # Qwen3: refused when set (scratchpad_amd/qwen3.py)
 
     @property
     def is_encoder_decoder(self) -> bool:
@@ -51,6 +54,8 @@ class ModelConfig:
     def __post_init__(self):
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
+        if self.architecture not in ("llama", "qwen3"):
+            raise ValueError(f"Unsupported architecture: {self.architecture!r} (llama, qwen3)")
 
     def get_num_kv_heads(self, tp_size: int) -> int:
         # model_config.py:155-163: replicate KV heads when tp > total_kv
@@ -86,6 +91,18 @@ class ModelConfig:
     def llama3_70b(cls, context_len: int = 8192):
         return cls(8192, 28672, 80, 64, 8, 128256, context_len=context_len,
                    max_position_embeddings=max(8192, context_len))
+
+    @classmethod
+    def qwen3_8b(cls, context_len: int = 8192):
+        return cls(4096, 12288, 36, 32, 8, 151936, context_len=context_len, head_dim=128, rms_norm_eps=1e-6,
+                   rope_theta=1000000.0, max_position_embeddings=max(40960, context_len), architecture="qwen3")
+
+    @classmethod
+    def qwen3_0_6b(cls, context_len: int = 8192):
+        """head_dim 128 with 16 heads over hidden 1024: q_size 2048 is twice the hidden size"""
+        return cls(1024, 3072, 28, 16, 8, 151936, context_len=context_len, head_dim=128, rms_norm_eps=1e-6,
+                   rope_theta=1000000.0, max_position_embeddings=max(40960, context_len),
+                   tie_word_embeddings=True, architecture="qwen3")
 
 
 @dataclass
@@ -153,6 +170,9 @@ class ModelRunner:
             if self.model_config.is_encoder_decoder:
                 from .mllama import MllamaForConditionalGeneration
                 self.model = MllamaForConditionalGeneration(self.model_config, dtype=self.dtype).eval()
+            elif self.model_config.architecture == "qwen3":
+                from .qwen3 import Qwen3ForCausalLM
+                self.model = Qwen3ForCausalLM(self.model_config, dtype=self.dtype).eval()
             else:
                 self.model = LlamaForCausalLM(self.model_config, dtype=self.dtype).eval()
         for p in self.model.parameters():
