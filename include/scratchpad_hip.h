@@ -87,6 +87,23 @@ SP_API int sp_fused_add_rmsnorm(void* x, void* residual, const void* weight, int
 SP_API int sp_silu_and_mul(void* out, const void* x, int64_t num_tokens, int d, int64_t x_stride,
                     int64_t out_stride, int dtype, void* stream);
 
+/* ---- xIELU, the activation of the ungated Apertus MLP (nn/layers/activation.py:34-60, XIELU.forward).
+ * out[t, j] = y(x[t, j]) for j < d, with ap = softplus(*alpha_p_raw), an = beta + softplus(*alpha_n_raw),
+ * softplus(v) = v > 20 ? v : log1p(exp(v)):
+ *     x > 0 :  y = ap * x * x + beta * x
+ *     else  :  y = an * expm1(min(x, eps)) - an * x + beta * x      (x == 0 gives an * expm1(eps), not 0)
+ * All arithmetic in fp32 from the stored inputs, ONE rounding to `dtype`.  alpha_p_raw / alpha_n_raw are DEVICE
+ * pointers to one element in `dtype` (the module's two parameters as a checkpoint loads them); the kernel reads them
+ * on every launch and nothing derived from them is kept on the host, so a captured launch follows a parameter that
+ * is overwritten between replays.  eps is the reference's stored constant, float(bfloat16(-1e-6)), in every dtype.
+ * Row strides in elements, >= d; columns >= d of out are never written; out == x is allowed.  Rows whose x and out
+ * addresses share their offset within 16 bytes move as 16-byte vectors with a scalar head and tail, other rows
+ * element by element, all in one launch.  fp32 / fp16 / bf16.
+ * SP_ERR_INVALID_ARG before any launch: d <= 0, num_tokens < 0, a NULL pointer, a stride below d, a pointer that
+ * is not device memory.  num_tokens == 0 is SP_OK without a launch.                                              */
+SP_API int sp_xielu(void* out, const void* x, const void* alpha_p_raw, const void* alpha_n_raw, float beta, float eps,
+             int64_t num_tokens, int d, int64_t x_stride, int64_t out_stride, int dtype, void* stream);
+
 /* ---- Rotary embedding, in place on q and k: replaces triteia_cuda.rotary_embedding
  *      (nn/layers/rotary_embedding.py:132-164; semantics of forward_native 102-130).
  * cos_sin_cache: [max_position, rotary_dim] = cos || sin, in `dtype`; positions int64 [T].
@@ -444,6 +461,16 @@ SP_API int sp_vocab_mask_apply(float* logits, int64_t row_stride, const void* ma
  *      act_fn (nn/models/llama/llama.py:62-66) in one launch.                                      */
 SP_API int sp_gemm_skinny(void* out, const void* x, const void* w, int M, int N, int K, int64_t x_stride,
                    int64_t w_stride, int64_t out_stride, int epilogue, int dtype, void* stream);
+/* sp_gemm_skinny_xielu: out[M, N] = xIELU(round(x . w^T)) - up_proj + act_fn of SwissAIMLP
+ *      (nn/models/swissai/apertus.py:63-68) in one launch, bit for bit sp_gemm_skinny(epilogue 0) followed by
+ *      sp_xielu on its result.  Shapes, strides and refusals are those of epilogue 0 (SP_ERR_UNSUPPORTED: M > 16,
+ *      K % 32 != 0, fp32: issue the two calls); alpha_p_raw, alpha_n_raw, beta, eps as in sp_xielu, the two
+ *      pointers required (non-NULL).  Like sp_gemm_skinny, and unlike sp_xielu, this entry does NOT ask the runtime
+ *      whether its pointers are device memory: it sits on the decode step, and the caller vouches for all five
+ *      (scratchpad_amd/_native.py refuses host tensors before the call).                                                                           */
+SP_API int sp_gemm_skinny_xielu(void* out, const void* x, const void* w, int M, int N, int K, int64_t x_stride,
+                         int64_t w_stride, int64_t out_stride, const void* alpha_p_raw, const void* alpha_n_raw,
+                         float beta, float eps, int dtype, void* stream);
 
 /* ---- Direct all-reduce through IPC-mapped peer regions: fills GroupCoordinator.ca_comm
  *      (distributed/parallel_state.py:266-267, 326-347; the reference never constructs one and always

@@ -59,6 +59,7 @@ SIGNATURES = {
     "sp_rmsnorm": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i64, _f32, _i32, _vp]),
     "sp_fused_add_rmsnorm": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i64, _f32, _i32, _vp]),
     "sp_silu_and_mul": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _i32, _vp]),
+    "sp_xielu": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _i64, _i32, _i64, _i64, _i32, _vp]),
     "sp_rotary_embedding": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64,
                                    _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
     "sp_qk_norm_rotary": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64,
@@ -110,6 +111,7 @@ SIGNATURES = {
     "sp_fused_allreduce_add_rmsnorm": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _i64, _f32, _i32, _vp, _i32, _i32,
                                               _sz, _i64, _vp, _vp]),
     "sp_gemm_skinny": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _vp]),
+    "sp_gemm_skinny_xielu": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _i32, _vp]),
 }
 
 
@@ -225,6 +227,53 @@ def silu_and_mul(x: torch.Tensor) -> torch.Tensor:
     _check(load().sp_silu_and_mul(out.data_ptr(), x2.data_ptr(), x2.shape[0], d, x2.stride(0),
                                   out.stride(0), _dt(x), _stream()), "sp_silu_and_mul")
     return out.view(*x.shape[:-1], d)
+
+
+# the constant XIELU.forward clamps with: the reference stores eps as a bf16 tensor whatever the model dtype, so every
+# run sees float(bfloat16(-1e-6)) and not -1e-6
+XIELU_EPS = -9.98377799987793e-07
+# calls by the path they took: "xielu" = an sp_xielu launch, "gemm_skinny_xielu" = one sp_gemm_skinny_xielu launch
+# (up_proj and the activation), "two_call" = the library refused the fused shape (SP_ERR_UNSUPPORTED) and linear_xielu
+# ran the projection and sp_xielu instead (tests: a decode step must count as gemm_skinny_xielu)
+XIELU_CALLS = {"xielu": 0, "gemm_skinny_xielu": 0, "two_call": 0}
+
+
+def _xielu_scalars(x: torch.Tensor, alpha_p: torch.Tensor, alpha_n: torch.Tensor, what: str):
+    """the two raw parameters as the kernel reads them: one element each, on the device, in the activation dtype"""
+    _gpu(x, alpha_p, alpha_n)
+    if alpha_p.numel() != 1 or alpha_n.numel() != 1:
+        raise RuntimeError(f"{what}: alpha_p and alpha_n hold one element each")
+    if alpha_p.dtype != x.dtype or alpha_n.dtype != x.dtype:
+        raise RuntimeError(f"{what}: alpha_p / alpha_n must be in the activation dtype {x.dtype}: the kernel reads "
+                           "them from device memory on every launch (nothing is converted or kept on the host)")
+
+
+def xielu(x: torch.Tensor, alpha_p: torch.Tensor, alpha_n: torch.Tensor, beta: float, eps: float = XIELU_EPS,
+          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """XIELU.forward (activation.py:53-60) over the last dimension of x; ``out`` may be x itself (in place) or any
+    [rows, >= d] row-contiguous tensor of x's dtype, of which columns >= d are left alone.  alpha_p / alpha_n are the
+    module's RAW parameters (softplus is applied by the kernel, on every launch)."""
+    _xielu_scalars(x, alpha_p, alpha_n, "xielu")
+    _gpu(out)
+    if out is x:
+        if x.dim() != 2 or x.stride(-1) != 1:
+            raise RuntimeError("xielu in place needs a 2-D row-contiguous x")
+        x2 = o2 = x
+    else:
+        x2 = _rows(x)
+        if out is None:
+            o2 = empty_rows(x2.shape[0], x2.shape[1], x.dtype, x.device)
+        else:
+            if out.dtype != x.dtype or out.dim() != 2 or out.stride(-1) != 1 or out.shape[0] != x2.shape[0]:
+                raise RuntimeError("xielu: out must be 2-D, row-contiguous, of x's dtype and row count")
+            o2 = out
+    d = x2.shape[1]
+    _check(load().sp_xielu(o2.data_ptr(), x2.data_ptr(), alpha_p.data_ptr(), alpha_n.data_ptr(), float(beta),
+                           float(eps), x2.shape[0], d, x2.stride(0), o2.stride(0), _dt(x), _stream()), "sp_xielu")
+    XIELU_CALLS["xielu"] += 1
+    if out is not None:
+        return out
+    return o2.view(x.shape)
 
 
 def rotary_embedding(positions: torch.Tensor, query: torch.Tensor, key: torch.Tensor,
@@ -1086,6 +1135,42 @@ def linear_silu_mul(x: torch.Tensor, gate_up_weight: torch.Tensor, any_rows: boo
     _check(load().sp_gemm_skinny(out.data_ptr(), x.data_ptr(), gate_up_weight.data_ptr(), M, inter, K, x.stride(0),
                                  gate_up_weight.stride(0), out.stride(0), 1, _dt(x), _stream()), "sp_gemm_skinny(silu)")
     return out
+
+
+def gemm_skinny_xielu(x: torch.Tensor, weight: torch.Tensor, alpha_p: torch.Tensor, alpha_n: torch.Tensor, beta: float,
+                      eps: float = XIELU_EPS) -> Optional[torch.Tensor]:
+    """xIELU(x @ weight.T) as ONE launch (sp_gemm_skinny_xielu): x [M, K], weight [N, K], result [M, N], bit for bit
+    sp_gemm_skinny(epilogue 0) followed by sp_xielu.  None when the library refuses the shape (more than 16 rows, K
+    not a multiple of 32, fp32): the caller runs the two steps.  Anything else it objects to raises."""
+    _xielu_scalars(x, alpha_p, alpha_n, "gemm_skinny_xielu")
+    _gpu(weight)
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1] or weight.dtype != x.dtype \
+            or x.stride(1) != 1 or weight.stride(1) != 1:
+        raise RuntimeError("gemm_skinny_xielu: x [M, K] and weight [N, K] must be row-contiguous and of one dtype")
+    M, K = x.shape
+    N = weight.shape[0]
+    out = empty_rows(M, N, x.dtype, x.device)
+    status = load().sp_gemm_skinny_xielu(out.data_ptr(), x.data_ptr(), weight.data_ptr(), M, N, K, x.stride(0),
+                                         weight.stride(0), out.stride(0), alpha_p.data_ptr(), alpha_n.data_ptr(),
+                                         float(beta), float(eps), _dt(x), _stream())
+    if status == SP_ERR_UNSUPPORTED:
+        return None
+    _check(status, "sp_gemm_skinny_xielu")
+    XIELU_CALLS["gemm_skinny_xielu"] += 1
+    return out
+
+
+def linear_xielu(x: torch.Tensor, weight: torch.Tensor, alpha_p: torch.Tensor, alpha_n: torch.Tensor, beta: float,
+                 eps: float = XIELU_EPS) -> torch.Tensor:
+    """SwissAIMLP's up_proj + act_fn: at most SKINNY_MAX_ROWS rows take the fused launch; above that, or where the
+    library refuses the shape, the projection (``linear``) and then xielu in place on its result."""
+    if _SKINNY_ON and x.is_cuda and x.dim() == 2 and 0 < x.shape[0] <= SKINNY_MAX_ROWS:
+        out = gemm_skinny_xielu(x, weight, alpha_p, alpha_n, beta, eps)
+        if out is not None:
+            return out
+        XIELU_CALLS["two_call"] += 1
+    up = linear(x, weight)
+    return xielu(up, alpha_p, alpha_n, beta, eps, out=up)
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:

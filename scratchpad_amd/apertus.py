@@ -1,0 +1,179 @@
+"""Apertus (SwissAI) decoder hosted on the HIP hot path.
+
+Re-hosts nn/models/swissai/apertus.py (SwissAIMLP 31-68, SwissAIAttention 71-176, SwissAIDecoderLayer 179-257,
+SwissAIModel 260-308, SwissAIForCausalLM 311-450): the reference's module tree and parameter names -
+``attention_layernorm`` / ``feedforward_layernorm`` for the two layer norms, ``self_attn.q_norm`` / ``k_norm``,
+``mlp.up_proj`` / ``mlp.down_proj`` and the two raw activation scalars ``mlp.act_fn.alpha_p`` / ``alpha_n`` - so its
+checkpoints and state_dicts map 1:1.
+
+The attention block is Qwen3's: per-head RMSNorm of q and k, rotary embedding, KV store - one sp_qk_norm_rotary launch
+on the fused path, the reference's order of separate steps on the other.  SwissAIAttention is qwen3.py's class under
+the reference's constructor; nothing of it is restated here.  The sharded linears, the logits processor, the deferred
+all-reduce protocol under tensor parallelism and the state_dict loader are llama.py's.
+
+What is new is the MLP: ``up_proj -> xIELU -> down_proj`` with no gate projection (apertus.py:63-68).  up_proj is
+column-parallel with a single shard, down_proj row-parallel, and the two activation scalars are replicated on every
+tensor-parallel rank.  A step of at most 16 rows runs up_proj and the activation as ONE weight-streaming launch
+(sp_gemm_skinny_xielu), bit for bit the skinny projection followed by sp_xielu; above that the projection is the
+library GEMM and sp_xielu runs in place on its result (_native.XIELU_CALLS says which ran).
+
+Refused with NotImplementedError: ``attention_bias`` / ``bias`` / ``qkv_bias`` / ``mlp_bias``, a
+``partial_rotary_factor`` other than 1, a ``hidden_act`` other than "xielu".  The reference's ``get_embedding`` /
+pooler branch (apertus.py:336, 353-354) is not built: ``forward(get_embedding=True)`` raises."""
+from typing import Any, Dict, Iterable, Optional, Tuple
+
+import torch
+from torch import nn
+
+from . import _native
+from .distributed import get_tensor_model_parallel_world_size
+from .forward_info import ForwardBatch
+from .layers import RMSNorm, XIELU
+from .llama import (LlamaForCausalLM, LogitsProcessor, LogitsProcessorOutput, MergedColumnParallelLinear,
+                    ParallelLMHead, RowParallelLinear, VocabParallelEmbedding, norm_after_row_parallel)
+from .qwen3 import Qwen3Attention
+
+
+class SwissAIMLP(nn.Module):
+    def __init__(self, hidden_size: int, intermediate_size: int, hidden_act: str, bias: bool = False, dtype=None):
+        super().__init__()
+        if bias:
+            raise NotImplementedError("mlp_bias=True (a bias on up_proj / down_proj) is not built")
+        if hidden_act != "xielu":
+            raise NotImplementedError(f"hidden_act={hidden_act!r} is not built for this architecture: only xielu")
+        self.up_proj = MergedColumnParallelLinear(hidden_size, [intermediate_size], dtype)
+        self.down_proj = RowParallelLinear(intermediate_size, hidden_size, dtype)
+        self.act_fn = XIELU()
+
+    def forward(self, x, reduce_output: bool = True):
+        # note: with xielu, there's no gate_proj.  <= 16 rows: projection and activation in one launch
+        act = self.act_fn
+        x = _native.linear_xielu(x, self.up_proj.weight, act.alpha_p.data, act.alpha_n.data, act.beta, act.eps)
+        x, _ = self.down_proj(x, reduce_output)
+        return x
+
+
+class SwissAIAttention(Qwen3Attention):
+    """apertus.py:71-176 is Qwen3Attention with the head size and the norm epsilon read from the config"""
+
+    def __init__(self, hidden_size: int, config, num_heads: int, num_kv_heads: int, layer_id: int = 0,
+                 rope_theta: float = 10000, rope_scaling: Optional[Dict[str, Any]] = None,
+                 max_position_embeddings: int = 8192, bias: bool = False, bias_o_proj: bool = False, dtype=None):
+        if getattr(config, "partial_rotary_factor", 1) != 1:
+            raise NotImplementedError("partial_rotary_factor != 1 is not built: q_norm / k_norm and the rotation "
+                                      "share one fused launch over the whole head")
+        super().__init__(hidden_size, num_heads, num_kv_heads, layer_id=layer_id, rope_theta=rope_theta,
+                         rope_scaling=rope_scaling, head_dim=getattr(config, "head_dim", None),
+                         max_position_embeddings=max_position_embeddings, rms_norm_eps=config.rms_norm_eps,
+                         attention_bias=bool(bias or bias_o_proj), dtype=dtype)
+        self.layer_id = layer_id
+
+
+class SwissAIDecoderLayer(nn.Module):
+    def __init__(self, config, layer_id: int = 0, dtype=None):
+        super().__init__()
+        self.hidden_size = config.hidden_size
+        rope_scaling = getattr(config, "rope_scaling", None)
+        if rope_scaling is not None and getattr(config, "original_max_position_embeddings", None):
+            rope_scaling = dict(rope_scaling,
+                                original_max_position_embeddings=config.original_max_position_embeddings)
+        attention_bias = getattr(config, "attention_bias", False) or getattr(config, "bias", False)
+        bias_o_proj = attention_bias
+        if hasattr(config, "qkv_bias"):
+            attention_bias = config.qkv_bias
+        self.self_attn = SwissAIAttention(
+            config=config, hidden_size=self.hidden_size, num_heads=config.num_attention_heads,
+            num_kv_heads=config.num_key_value_heads, layer_id=layer_id,
+            rope_theta=getattr(config, "rope_theta", 10000), rope_scaling=rope_scaling,
+            max_position_embeddings=getattr(config, "max_position_embeddings", 8192), bias=attention_bias,
+            bias_o_proj=bias_o_proj, dtype=dtype)
+        self.mlp = SwissAIMLP(self.hidden_size, config.intermediate_size, config.hidden_act,
+                              bias=getattr(config, "mlp_bias", False), dtype=dtype)
+        self.attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
+        self.feedforward_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
+
+    def forward(self, positions, hidden_states, forward_batch: ForwardBatch, residual: Optional[torch.Tensor],
+                defer_reduce: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """apertus.py:235-257 with llama.py's deferred all-reduce protocol (LlamaDecoderLayer.forward)."""
+        if residual is None:
+            residual = hidden_states
+            hidden_states = self.attention_layernorm(hidden_states)
+        elif defer_reduce:
+            hidden_states, residual = norm_after_row_parallel(self.attention_layernorm, hidden_states, residual)
+        else:
+            hidden_states, residual = self.attention_layernorm(hidden_states, residual)
+        hidden_states = self.self_attn(positions=positions, hidden_states=hidden_states,
+                                       forward_batch=forward_batch, reduce_output=not defer_reduce)
+        if defer_reduce:
+            hidden_states, residual = norm_after_row_parallel(self.feedforward_layernorm, hidden_states, residual)
+        else:
+            hidden_states, residual = self.feedforward_layernorm(hidden_states, residual)
+        hidden_states = self.mlp(hidden_states, reduce_output=not defer_reduce)
+        return hidden_states, residual
+
+
+class SwissAIModel(nn.Module):
+    def __init__(self, config, dtype=None):
+        super().__init__()
+        self.config = config
+        self.vocab_size = config.vocab_size
+        self.embed_tokens = VocabParallelEmbedding(config.vocab_size, config.hidden_size, dtype)
+        self.layers = nn.ModuleList(
+            [SwissAIDecoderLayer(config, i, dtype) for i in range(config.num_hidden_layers)])
+        self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
+
+    def forward(self, input_ids, positions, forward_batch: ForwardBatch,
+                input_embeds: torch.Tensor = None) -> torch.Tensor:
+        hidden_states = self.embed_tokens(input_ids) if input_embeds is None else input_embeds
+        residual = None
+        defer = get_tensor_model_parallel_world_size() > 1
+        for layer in self.layers:
+            hidden_states, residual = layer(positions, hidden_states, forward_batch, residual, defer)
+        if defer:
+            hidden_states, _ = norm_after_row_parallel(self.norm, hidden_states, residual)
+        else:
+            hidden_states, _ = self.norm(hidden_states, residual)
+        return hidden_states
+
+
+class SwissAIForCausalLM(nn.Module):
+    def __init__(self, config, dtype=None):
+        super().__init__()
+        self.config = config
+        self.model = SwissAIModel(config, dtype)
+        if getattr(config, "tie_word_embeddings", False):
+            self.lm_head = self.model.embed_tokens
+        else:
+            self.lm_head = ParallelLMHead(config.vocab_size, config.hidden_size, dtype)
+        self.logits_processor = LogitsProcessor(config)
+
+    @torch.no_grad()
+    def forward(self, input_ids, positions, forward_batch: ForwardBatch, input_embeds: torch.Tensor = None,
+                get_embedding: bool = False) -> LogitsProcessorOutput:
+        if get_embedding:
+            raise NotImplementedError("get_embedding=True (the reference's Pooler branch) is not built")
+        hidden_states = self.model(input_ids, positions, forward_batch, input_embeds)
+        return self.logits_processor(input_ids, hidden_states, self.lm_head, forward_batch)
+
+    # llama.py's loader goes by parameter names and ``shard_from_full`` alone: the norm weights and the two activation
+    # scalars of every layer have no shard_from_full and are copied whole, i.e. replicated on every rank
+    load_full_state_dict = LlamaForCausalLM.load_full_state_dict
+
+    def load_weights(self, weights: Iterable[Tuple[str, torch.Tensor]]) -> None:
+        """HF checkpoint names -> merged parameters (apertus.py:406-439): q_proj / k_proj / v_proj are stacked into
+        qkv_proj and nothing else is - up_proj stands alone.  A tied checkpoint's lm_head is skipped."""
+        tied = getattr(self.config, "tie_word_embeddings", False)
+        staged: Dict[str, Dict[str, torch.Tensor]] = {}
+        full: Dict[str, torch.Tensor] = {}
+        for name, w in weights:
+            if "rotary_emb.inv_freq" in name or (tied and "lm_head.weight" in name):
+                continue
+            for tag in ("q_proj", "k_proj", "v_proj"):
+                if "." + tag + "." in name:
+                    staged.setdefault(name.replace(tag, "qkv_proj"), {})[tag] = w
+                    break
+            else:
+                full[name] = w
+        for name, parts in staged.items():
+            full[name] = torch.cat([parts[t] for t in ("q_proj", "k_proj", "v_proj")], 0)
+        self.load_full_state_dict(full)

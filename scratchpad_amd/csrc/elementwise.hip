@@ -1,4 +1,4 @@
-// HBM-bound row kernels of the hot path: RMSNorm (+fused add), SiLU-mul, rotary (+fused KV
+// HBM-bound row kernels of the hot path: RMSNorm (+fused add), SiLU-mul, xIELU, rotary (+fused KV
 // store), KV store, req_to_token scatter, positions.  All vectorised to 16 B per lane
 // (cdna_hip_programming.md Guideline 13); each has a scalar twin for odd shapes / alignments.
 //
@@ -154,6 +154,58 @@ __global__ __launch_bounds__(kBlock) void silu_mul_scalar_kernel(void* __restric
     const int j = (int)(i - t * d);
     const float a = E::load(x, t * x_stride + j), b = E::load(x, t * x_stride + d + j);
     E::store(out, t * o_stride + j, __fmul_rn(E::round(silu_f32(a)), b));
+  }
+}
+
+// -------------------------------------------------------------------------------------- xIELU
+// nn/layers/activation.py:53-60 (xielu_ref, sp_common.h): fp32 from the stored input, one rounding.  A streaming
+// kernel: T*d read, T*d written.  A row is cut into d / V + 2 items (V = elements per 16 bytes).  Where the row's x and
+// out addresses share their offset within 16 bytes: item 0 is the scalar head up to the first 16-byte boundary, items
+// 1 .. nvec one 16-byte vector each, item nvec + 1 the scalar tail.  Otherwise (differently misaligned rows) item j is
+// elements [j V, j V + V) one by one.  Every element is read and written by the same lane, so out may alias x.
+template <typename Tag>
+__global__ __launch_bounds__(kBlock) void xielu_kernel(void* out, const void* x, const void* alpha_p_raw,
+                                                        const void* alpha_n_raw, float beta, float eps,
+                                                        int64_t num_tokens, int d, int64_t x_stride,
+                                                        int64_t o_stride) {
+  typedef Elem<Tag> E;
+  constexpr int V = E::kVec;
+  const XieluCoef c = xielu_coef<Tag>(alpha_p_raw, alpha_n_raw, beta, eps);
+  const int items = d / V + 2;
+  const int64_t total = num_tokens * items;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * kBlock) {
+    const int64_t t = i / items;
+    const int j = (int)(i - t * items);
+    const char* xrow = (const char*)x + t * x_stride * E::kBytes;
+    char* orow = (char*)out + t * o_stride * E::kBytes;
+    const int mis = (int)((uintptr_t)xrow & 15);
+    int lo, hi;
+    bool vec = false;
+    if (mis == (int)((uintptr_t)orow & 15) && mis % E::kBytes == 0) {
+      const int head = min(d, ((16 - mis) & 15) / E::kBytes);
+      const int nvec = (d - head) / V;
+      if (j == 0) {
+        lo = 0, hi = head;
+      } else if (j <= nvec) {
+        lo = head + (j - 1) * V, hi = lo + V, vec = true;
+      } else if (j == nvec + 1) {
+        lo = head + nvec * V, hi = d;
+      } else {
+        lo = hi = 0;
+      }
+    } else {
+      lo = min(d, j * V), hi = min(d, lo + V);
+    }
+    if (vec) {
+      float a[V], y[V];
+      unpack16<Tag>(ld16(xrow + (int64_t)lo * E::kBytes), a);
+#pragma unroll
+      for (int e = 0; e < V; ++e) y[e] = xielu_ref(a[e], c);
+      st16(orow + (int64_t)lo * E::kBytes, pack16<Tag>(y));
+    } else {
+      for (int e = lo; e < hi; ++e) E::store(orow, e, xielu_ref(E::load(xrow, e), c));
+    }
   }
 }
 
@@ -641,6 +693,40 @@ extern "C" int sp_silu_and_mul(void* out, const void* x, int64_t num_tokens, int
   SP_CHECK_ARG(out && x);
   SP_DISPATCH_DTYPE(dtype, return (launch_silu<Tag>(out, x, num_tokens, d, x_stride, out_stride,
                                                      (hipStream_t)stream)));
+}
+
+template <typename Tag>
+static int launch_xielu(void* out, const void* x, const void* ap, const void* an, float beta, float eps, int64_t T,
+                        int d, int64_t xs, int64_t os, hipStream_t st) {
+  const int64_t work = T * (d / Elem<Tag>::kVec + 2);
+  int64_t blocks = (work + kBlock - 1) / kBlock;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  xielu_kernel<Tag><<<dim3((unsigned)blocks), kBlock, 0, st>>>(out, x, ap, an, beta, eps, T, d, xs, os);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+// device (or managed) memory: the two activation parameters and the activations are read by the kernel, never here
+static bool on_device(const void* p) {
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();      // an unknown address is an answer, not a launch failure
+    return false;
+  }
+  return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
+
+extern "C" int sp_xielu(void* out, const void* x, const void* alpha_p_raw, const void* alpha_n_raw, float beta,
+                        float eps, int64_t num_tokens, int d, int64_t x_stride, int64_t out_stride, int dtype,
+                        void* stream) {
+  SP_CHECK_ARG(num_tokens >= 0 && d > 0);
+  if (num_tokens == 0) return SP_OK;
+  SP_CHECK_ARG(out && x && alpha_p_raw && alpha_n_raw);
+  SP_CHECK_ARG(x_stride >= d && out_stride >= d);
+  if (dtype != SP_F32 && dtype != SP_F16 && dtype != SP_BF16) return SP_ERR_UNSUPPORTED;
+  SP_CHECK_ARG(on_device(out) && on_device(x) && on_device(alpha_p_raw) && on_device(alpha_n_raw));
+  SP_DISPATCH_DTYPE(dtype, return (launch_xielu<Tag>(out, x, alpha_p_raw, alpha_n_raw, beta, eps, num_tokens, d,
+                                                      x_stride, out_stride, (hipStream_t)stream)));
 }
 
 template <typename Tag>

@@ -26,6 +26,11 @@
 // the activation in the PROLOGUE of the down projection, every workgroup recomputing the M x K activations it
 // streams - was built first and measured 2 x SLOWER than the two launches: 76 vs 38 us at 1 row; the exponentials
 // of all 16 lane rows of every k-step are vector work the stream cannot hide.  profiles/NOTES.md, round 4.)
+//
+// `EPI` = 2 (sp_gemm_skinny_xielu): the ungated MLP of Apertus (nn/models/swissai/apertus.py:63-68): the plain tile of
+// epilogue 0, and the lanes that finish a column apply xielu_ref (sp_common.h) to the ROUNDED sum - bit for bit the
+// plain projection followed by sp_xielu.  The two raw activation parameters are read from device memory by every
+// launch (one element each, in the activation dtype).
 #include "sp_common.h"
 
 namespace sp {
@@ -53,6 +58,9 @@ struct SkinnyArgs {
   void* out;
   int M, N, K;
   int64_t x_stride, w_stride, out_stride;   // elements
+  const void* alpha_p_raw;                  // EPI 2 only: xIELU's parameters and constants
+  const void* alpha_n_raw;
+  float beta, eps;
 };
 
 constexpr int kSkWaves = 8;
@@ -72,12 +80,14 @@ __device__ __forceinline__ u32x4 ld16_nt(const void* p) { return __builtin_nonte
 template <typename Tag, int NB, int UNROLL, bool NT, int EPI>
 __global__ __launch_bounds__(kSkWaves * 64) void gemm_skinny_kernel(SkinnyArgs a) {
   typedef Elem<Tag> E;
-  static_assert(EPI == 0 || NB == 1, "the SiLU-mul epilogue pairs the two halves of one 16-row tile");
+  static_assert(EPI != 1 || NB == 1, "the SiLU-mul epilogue pairs the two halves of one 16-row tile");
   __shared__ float red[kSkWaves][NB][16 * 17];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r16 = lane & 15, q = lane >> 4;            // operand row / k-quarter of the lane
   const int n0 = EPI == 1 ? blockIdx.x * 8 : blockIdx.x * 16 * NB;
   const bool mrow = r16 < a.M;
+  float raw_p = 0.f, raw_n = 0.f;                      // read ahead of the stream, used by the lanes that store
+  if constexpr (EPI == 2) raw_p = E::load(a.alpha_p_raw, 0), raw_n = E::load(a.alpha_n_raw, 0);
   const char* wp[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -120,6 +130,8 @@ __global__ __launch_bounds__(kSkWaves * 64) void gemm_skinny_kernel(SkinnyArgs a
     for (int r = 0; r < 4; ++r) red[wave][nb][(4 * q + r) * 17 + r16] = acc[nb][r];
   __syncthreads();
   for (int nb = wave; nb < NB; nb += kSkWaves) {
+    XieluCoef xc;
+    if constexpr (EPI == 2) xc = xielu_coef_of(raw_p, raw_n, a.beta, a.eps);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int col = 4 * q + r;
@@ -137,6 +149,7 @@ __global__ __launch_bounds__(kSkWaves * 64) void gemm_skinny_kernel(SkinnyArgs a
           E::store(a.out, (int64_t)r16 * a.out_stride + n, __fmul_rn(E::round(silu_ref(E::round(s))), E::round(su)));
       } else {
         const int n = n0 + 16 * nb + col;
+        if constexpr (EPI == 2) s = xielu_ref(E::round(s), xc);
         if (mrow && n < a.N) E::store(a.out, (int64_t)r16 * a.out_stride + n, s);
       }
     }
@@ -154,7 +167,9 @@ template <typename Tag>
 static void launch_skinny(const SkinnyArgs& a, int epilogue, hipStream_t st) {
   const dim3 block(kSkWaves * 64);
   const bool u16 = g_skinny_u16 && (a.K / 32) % (16 * kSkWaves) == 0;
-  if (epilogue == 1 && u16) gemm_skinny_kernel<Tag, 1, 16, false, 1><<<dim3((a.N + 7) / 8), block, 0, st>>>(a);
+  if (epilogue == 2 && u16) gemm_skinny_kernel<Tag, 1, 16, false, 2><<<dim3((a.N + 15) / 16), block, 0, st>>>(a);
+  else if (epilogue == 2) gemm_skinny_kernel<Tag, 1, 8, false, 2><<<dim3((a.N + 15) / 16), block, 0, st>>>(a);
+  else if (epilogue == 1 && u16) gemm_skinny_kernel<Tag, 1, 16, false, 1><<<dim3((a.N + 7) / 8), block, 0, st>>>(a);
   else if (epilogue == 1) gemm_skinny_kernel<Tag, 1, 8, false, 1><<<dim3((a.N + 7) / 8), block, 0, st>>>(a);
   else if (u16) gemm_skinny_kernel<Tag, 1, 16, false, 0><<<dim3((a.N + 15) / 16), block, 0, st>>>(a);
   else if (g_skinny_nt) gemm_skinny_kernel<Tag, 1, 8, true, 0><<<dim3((a.N + 15) / 16), block, 0, st>>>(a);
@@ -172,9 +187,28 @@ extern "C" int sp_gemm_skinny(void* out, const void* x, const void* w, int M, in
   if (dtype != SP_BF16 && dtype != SP_F16) return SP_ERR_UNSUPPORTED;
   SP_CHECK_ARG(x_stride % 8 == 0 && w_stride % 8 == 0 && x_stride >= K && w_stride >= K && out_stride >= N);
   SP_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0);
-  sp::SkinnyArgs a{(const char*)x, (const char*)w, out, M, N, K, x_stride, w_stride, out_stride};
+  sp::SkinnyArgs a{(const char*)x, (const char*)w, out, M, N, K, x_stride, w_stride, out_stride, nullptr, nullptr,
+                   0.f, 0.f};
   if (dtype == SP_BF16) sp::launch_skinny<sp::bf16_tag>(a, epilogue, (hipStream_t)stream);
   else sp::launch_skinny<sp::f16_tag>(a, epilogue, (hipStream_t)stream);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+extern "C" int sp_gemm_skinny_xielu(void* out, const void* x, const void* w, int M, int N, int K, int64_t x_stride,
+                                    int64_t w_stride, int64_t out_stride, const void* alpha_p_raw,
+                                    const void* alpha_n_raw, float beta, float eps, int dtype, void* stream) {
+  SP_CHECK_ARG(M >= 0 && N >= 0 && K > 0);
+  if (M == 0 || N == 0) return SP_OK;
+  SP_CHECK_ARG(out && x && w && alpha_p_raw && alpha_n_raw);
+  if (M > 16 || K % 32 != 0) return SP_ERR_UNSUPPORTED;
+  if (dtype != SP_BF16 && dtype != SP_F16) return SP_ERR_UNSUPPORTED;
+  SP_CHECK_ARG(x_stride % 8 == 0 && w_stride % 8 == 0 && x_stride >= K && w_stride >= K && out_stride >= N);
+  SP_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0);
+  sp::SkinnyArgs a{(const char*)x, (const char*)w, out, M, N, K, x_stride, w_stride, out_stride, alpha_p_raw,
+                   alpha_n_raw, beta, eps};
+  if (dtype == SP_BF16) sp::launch_skinny<sp::bf16_tag>(a, 2, (hipStream_t)stream);
+  else sp::launch_skinny<sp::f16_tag>(a, 2, (hipStream_t)stream);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

@@ -146,6 +146,33 @@ __device__ __forceinline__ u32x4 pack16<f16_tag>(const float* f) {
 // fused prologue of sp_gemm_skinny, which must agree bit for bit)
 __device__ __forceinline__ float silu_ref(float a) { return __fdiv_rn(a, __fadd_rn(1.0f, expf(-a))); }
 
+// xIELU as XIELU.forward states it (nn/layers/activation.py:53-60), in fp32 with every operation rounded on its own
+// whatever the translation unit's contraction mode (shared by sp_xielu and the epilogue of sp_gemm_skinny_xielu, which
+// must agree bit for bit).  The two raw parameters are read from device memory by the kernel that uses them.
+struct XieluCoef {
+  float ap, an, bma, beta, eps;   // softplus(alpha_p_raw), beta + softplus(alpha_n_raw), beta - an
+};
+__device__ __forceinline__ float softplus_ref(float v) { return v > 20.0f ? v : log1pf(expf(v)); }   // torch's threshold
+__device__ __forceinline__ XieluCoef xielu_coef_of(float raw_p, float raw_n, float beta, float eps) {
+  XieluCoef c;
+  c.ap = softplus_ref(raw_p);
+  c.an = __fadd_rn(beta, softplus_ref(raw_n));
+  c.bma = __fsub_rn(beta, c.an);
+  c.beta = beta;
+  c.eps = eps;
+  return c;
+}
+template <typename Tag>
+__device__ __forceinline__ XieluCoef xielu_coef(const void* alpha_p_raw, const void* alpha_n_raw, float beta,
+                                                float eps) {
+  return xielu_coef_of(Elem<Tag>::load(alpha_p_raw, 0), Elem<Tag>::load(alpha_n_raw, 0), beta, eps);
+}
+// x > 0: ap x x + beta x; else an expm1(min(x, eps)) - an x + beta x (x == 0 lands here: an expm1(eps), not 0)
+__device__ __forceinline__ float xielu_ref(float x, const XieluCoef& c) {
+  if (x > 0.0f) return __fmaf_rn(__fmul_rn(c.ap, x), x, __fmul_rn(c.beta, x));
+  return __fmaf_rn(c.an, expm1f(fminf(x, c.eps)), __fmul_rn(c.bma, x));
+}
+
 __device__ __forceinline__ u32x4 ld16(const void* p) { return *(const u32x4*)p; }
 __device__ __forceinline__ void st16(void* p, const u32x4& v) { *(u32x4*)p = v; }
 

@@ -1,6 +1,6 @@
-"""RMSNorm / SiluAndMul / rotary embedding modules over the HIP kernels.
+"""RMSNorm / SiluAndMul / XIELU / rotary embedding modules over the HIP kernels.
 
-Mirrors nn/layers/layernorm.py:12-32, nn/layers/activation.py:21-31 and
+Mirrors nn/layers/layernorm.py:12-32, nn/layers/activation.py:21-60 and
 nn/layers/rotary_embedding.py:52-170, 677-720, 918-1088 (same class names, constructor
 arguments, return conventions and in-place contracts)."""
 import math
@@ -35,6 +35,25 @@ class SiluAndMul(CustomOp):
 
     def forward_hip(self, x: torch.Tensor) -> torch.Tensor:
         return _native.silu_and_mul(x)
+
+
+class XIELU(CustomOp):
+    """activation.py:34-60.  The two learnable scalars are kept RAW, as the reference keeps them (softplus is applied
+    in the forward pass): alpha_p = log(e^alpha_p_init - 1), alpha_n = log(e^(alpha_n_init - beta) - 1), each of shape
+    [1].  The kernel reads them from device memory on every launch, so they must be in the activation dtype (a
+    checkpoint loaded in the model dtype leaves them so); ``eps`` is held as the reference holds it, rounded to bf16.
+    ``forward_hip(x, out=x)`` is in place."""
+
+    def __init__(self, alpha_p_init: float = 0.8, alpha_n_init: float = 0.8, beta: float = 0.5,
+                 eps: float = -1e-6) -> None:
+        super().__init__()
+        self.alpha_p = nn.Parameter(torch.log(torch.exp(torch.tensor(alpha_p_init)) - 1.0).unsqueeze(0))
+        self.alpha_n = nn.Parameter(torch.log(torch.exp(torch.tensor(alpha_n_init - beta)) - 1.0).unsqueeze(0))
+        self.beta = beta
+        self.eps = float(torch.tensor(eps, dtype=torch.bfloat16, device="cpu"))
+
+    def forward_hip(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return _native.xielu(x, self.alpha_p.data, self.alpha_n.data, self.beta, self.eps, out=out)
 
 
 class RotaryEmbedding(CustomOp):

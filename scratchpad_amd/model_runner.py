@@ -43,7 +43,7 @@ class ModelConfig:
     pad_token_id: Optional[int] = None
     # Mllama: the vision tower's config (MllamaVisionConfig fields); None = text side only
     vision_config: Optional[object] = None
-    # which decoder load_model builds: "llama" (with cross_attention_layers: Mllama) or "qwen3"
+    # which decoder load_model builds: "llama" (with cross_attention_layers: Mllama), "qwen3" or "apertus"
     architecture: str = "llama"
     attention_bias: bool = False        # Qwen3: refused when set (scratchpad_amd/qwen3.py)
 
@@ -54,8 +54,8 @@ class ModelConfig:
     def __post_init__(self):
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
-        if self.architecture not in ("llama", "qwen3"):
-            raise ValueError(f"Unsupported architecture: {self.architecture!r} (llama, qwen3)")
+        if self.architecture not in ("llama", "qwen3", "apertus"):
+            raise ValueError(f"Unsupported architecture: {self.architecture!r} (llama, qwen3, apertus)")
 
     def get_num_kv_heads(self, tp_size: int) -> int:
         # model_config.py:155-163: replicate KV heads when tp > total_kv
@@ -103,6 +103,16 @@ class ModelConfig:
         return cls(1024, 3072, 28, 16, 8, 151936, context_len=context_len, head_dim=128, rms_norm_eps=1e-6,
                    rope_theta=1000000.0, max_position_embeddings=max(40960, context_len),
                    tie_word_embeddings=True, architecture="qwen3")
+
+    @classmethod
+    def apertus_8b(cls, context_len: int = 8192):
+        """Apertus-8B: an ungated xIELU MLP of width 21504 under Qwen3's attention block.  The figures are written
+        from memory of the released configuration and are NOT verified against it."""
+        return cls(4096, 21504, 32, 32, 8, 131072, context_len=context_len, head_dim=128, rms_norm_eps=1e-5,
+                   rope_theta=12000000.0,
+                   rope_scaling={"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0,
+                                 "high_freq_factor": 4.0, "original_max_position_embeddings": 8192},
+                   max_position_embeddings=max(65536, context_len), hidden_act="xielu", architecture="apertus")
 
 
 @dataclass
@@ -173,6 +183,9 @@ class ModelRunner:
             elif self.model_config.architecture == "qwen3":
                 from .qwen3 import Qwen3ForCausalLM
                 self.model = Qwen3ForCausalLM(self.model_config, dtype=self.dtype).eval()
+            elif self.model_config.architecture == "apertus":
+                from .apertus import SwissAIForCausalLM
+                self.model = SwissAIForCausalLM(self.model_config, dtype=self.dtype).eval()
             else:
                 self.model = LlamaForCausalLM(self.model_config, dtype=self.dtype).eval()
         for p in self.model.parameters():
@@ -183,6 +196,8 @@ class ModelRunner:
             for name, p in self.model.named_parameters():
                 if "norm" in name:
                     p.data.fill_(1.0)
+                elif "act_fn.alpha" in name:  # xIELU's raw scalars keep XIELU()'s initial values
+                    pass
                 elif p.numel() == 1:          # Mllama tanh gates
                     p.data.fill_(0.5)
                 else:
