@@ -472,6 +472,34 @@ SP_API int sp_gemm_skinny_xielu(void* out, const void* x, const void* w, int M, 
                          int64_t w_stride, int64_t out_stride, const void* alpha_p_raw, const void* alpha_n_raw,
                          float beta, float eps, int dtype, void* stream);
 
+/* ---- LoRA toppings (additive in ABI 10): the per-row adapter products of the topping layers
+ *      (nn/toppings/topping_layer.py:41-348), which the reference hands to triteia.python.ops.ldmm or runs as one
+ *      masked torch product per adapter of the batch.  indices: int32 [num_tokens], the adapter slot of every row
+ *      (ToppingsManager.prepare_topping_batch); a row whose index is < 0 (the reference's -1: base model only) or
+ *      >= num_slots is SKIPPED: nothing of it is read or written, and no address is formed from its index.
+ *      Buffers keep the reference's layout (memory/topping_pool.py:88-124): a[slot] is [K, R] with R contiguous,
+ *      b[slot] is [r, num_slices * n] with the columns contiguous; slot strides in elements.
+ * sp_lora_shrink:  tmp[t, :R] = scale * (x[t, :K] . a[idx[t]])   fp32 [num_tokens, R], NOT rounded to `dtype`;
+ *      R = (stacked slices) * r: 3 r for qkv_proj, 2 r for gate_up_proj.  scale = lora_alpha / r.
+ * sp_lora_expand:  y[t, s n + c] += tmp[t, s r : (s+1) r] . b[idx[t]][:, s n + c]  for s < num_slices, c < n;
+ *      y and tmp are passed already offset to the first column they touch.  y is read and written in `dtype`; per
+ *      output ONE fp32 chain over j ascending, y = round(y + chain).  Columns >= num_slices * n of y are never touched.
+ * Batch invariance: the bits a row receives depend on that row's x, y, index and adapter only - not on num_tokens,
+ *      the row's position or its neighbours (the summation order is a function of (K, R, r) alone).
+ * SP_ERR_UNSUPPORTED: dtype other than fp16 / bf16; K or n not a positive multiple of 8; R not a positive multiple
+ *      of 8 or above 192; r not in {8, 16, 32, 64}; num_slices * r above 192.
+ * SP_ERR_INVALID_ARG before any launch: a negative size, a NULL pointer, x_stride < K, tmp_stride < R (resp.
+ *      num_slices * r), a_slot_stride < K * R, y_stride < num_slices * n, b_slot_stride < r * num_slices * n,
+ *      x / a / y / b not 16-byte aligned or x_stride / y_stride / a slot stride not a multiple of 8 (16-byte vectors),
+ *      tmp not 4-byte aligned.  num_tokens == 0 is SP_OK without a launch.  Like sp_gemm_skinny these entries sit on
+ *      the decode step and do not ask the runtime whether their pointers are device memory.                        */
+SP_API int sp_lora_shrink(float* tmp, const void* x, const void* a, const int32_t* indices, int64_t num_tokens,
+                   int K, int R, int num_slots, int64_t x_stride, int64_t a_slot_stride, int64_t tmp_stride,
+                   float scale, int dtype, void* stream);
+SP_API int sp_lora_expand(void* y, const float* tmp, const void* b, const int32_t* indices, int64_t num_tokens,
+                   int r, int n, int num_slices, int num_slots, int64_t y_stride, int64_t tmp_stride,
+                   int64_t b_slot_stride, int dtype, void* stream);
+
 /* ---- Direct all-reduce through IPC-mapped peer regions: fills GroupCoordinator.ca_comm
  *      (distributed/parallel_state.py:266-267, 326-347; the reference never constructs one and always
  *      calls NCCL, linear.py:1148-1149).  Each rank sp_ar_alloc()s one fine-grained region of

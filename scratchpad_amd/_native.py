@@ -112,6 +112,8 @@ SIGNATURES = {
                                               _sz, _i64, _vp, _vp]),
     "sp_gemm_skinny": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _vp]),
     "sp_gemm_skinny_xielu": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _i32, _vp]),
+    "sp_lora_shrink": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
+    "sp_lora_expand": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
 }
 
 
@@ -1211,3 +1213,72 @@ def linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
 
 def _feeds_a_measured_shape(width: int) -> bool:
     return any(k == width for (_n, k) in _LIBRARY_ROWS)
+
+
+# --------------------------------------------------------------------------- LoRA toppings
+# launches by entry ("shrink" = sp_lora_shrink, "expand" = sp_lora_expand): tests prove with it that a step ran the
+# kernels (at capture time for a graph) and that a runner without a manager runs none
+LORA_CALLS = {"shrink": 0, "expand": 0}
+LORA_RANKS = (8, 16, 32, 64)
+LORA_MAX_R = 192
+
+
+def _lora_indices(indices: torch.Tensor, rows: int, what: str) -> None:
+    if indices.dtype != torch.int32 or indices.dim() != 1 or indices.shape[0] < rows or \
+            (indices.shape[0] > 1 and indices.stride(0) != 1):
+        raise RuntimeError(f"{what}: indices must be a contiguous int32 vector of at least {rows} entries")
+
+
+def lora_shrink(x: torch.Tensor, A: torch.Tensor, indices: torch.Tensor, scale: float,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tmp[t] = scale * (x[t] @ A[indices[t]]) in fp32 (sp_lora_shrink): x [T, K] row-contiguous, A [slots, K, R]
+    (ToppingMemPool.A_buffer[module][layer]: R contiguous), indices int32 [>= T]; rows whose index is < 0 or >= slots
+    are left alone.  ``out``: fp32 [T, >= R] with contiguous rows, written in its first R columns; without it a new
+    UNINITIALISED [T, R] tensor (no fill launch: lora_expand never reads the tmp of a skipped row)."""
+    _gpu(x, A, indices, out)
+    if x.dim() != 2 or A.dim() != 3 or x.stride(1) != 1 or A.dtype != x.dtype or A.shape[1] != x.shape[1] \
+            or A.stride(2) != 1 or A.stride(1) != A.shape[2]:
+        raise RuntimeError("lora_shrink: x [T, K] row-contiguous and A [slots, K, R] with contiguous [K, R] slots, "
+                           f"of one dtype; got x {tuple(x.shape)} {x.dtype}, A {tuple(A.shape)} {A.dtype} "
+                           f"strides {tuple(A.stride())}")
+    T, K = x.shape
+    R = A.shape[2]
+    _lora_indices(indices, T, "lora_shrink")
+    if out is None:
+        out = torch.empty((T, R), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != T or out.shape[1] < R or out.stride(1) != 1:
+        raise RuntimeError("lora_shrink: out must be fp32 [T, >= R] with contiguous rows")
+    if T == 0:
+        return out
+    _check(load().sp_lora_shrink(out.data_ptr(), x.data_ptr(), A.data_ptr(), indices.data_ptr(), T, K, R, A.shape[0],
+                                 x.stride(0), A.stride(0), out.stride(0), float(scale), _dt(x), _stream()),
+           "sp_lora_shrink")
+    LORA_CALLS["shrink"] += 1
+    return out
+
+
+def lora_expand(y: torch.Tensor, tmp: torch.Tensor, B: torch.Tensor, indices: torch.Tensor,
+                num_slices: int) -> torch.Tensor:
+    """y[t, s n + c] += tmp[t, s r:(s+1) r] @ B[indices[t]][:, s n + c] in place (sp_lora_expand): y [T, >= S n] (a
+    column view of a wider activation is fine: its stride is passed), tmp fp32 [T, >= S r] (likewise), B [slots, r,
+    S n] (ToppingMemPool.B_buffer[module][layer]).  Rows whose index is < 0 or >= slots are left alone."""
+    _gpu(y, tmp, B, indices)
+    S = int(num_slices)
+    if y.dim() != 2 or tmp.dim() != 2 or B.dim() != 3 or y.stride(1) != 1 or tmp.stride(1) != 1 \
+            or tmp.dtype != torch.float32 or B.dtype != y.dtype or tmp.shape[0] != y.shape[0] \
+            or B.stride(2) != 1 or B.stride(1) != B.shape[2] or S < 1 or B.shape[2] % S != 0:
+        raise RuntimeError("lora_expand: y [T, >= S n] and fp32 tmp [T, >= S r] with contiguous rows, B [slots, r, "
+                           f"S n] with contiguous [r, S n] slots in y's dtype; got y {tuple(y.shape)} {y.dtype}, tmp "
+                           f"{tuple(tmp.shape)} {tmp.dtype}, B {tuple(B.shape)} {B.dtype}, num_slices {num_slices}")
+    T = y.shape[0]
+    r, n = B.shape[1], B.shape[2] // S
+    if y.shape[1] < S * n or tmp.shape[1] < S * r:
+        raise RuntimeError(f"lora_expand: y has {y.shape[1]} columns for {S * n}, tmp {tmp.shape[1]} for {S * r}")
+    _lora_indices(indices, T, "lora_expand")
+    if T == 0:
+        return y
+    _check(load().sp_lora_expand(y.data_ptr(), tmp.data_ptr(), B.data_ptr(), indices.data_ptr(), T, r, n, S,
+                                 B.shape[0], y.stride(0), tmp.stride(0), B.stride(0), _dt(y), _stream()),
+           "sp_lora_expand")
+    LORA_CALLS["expand"] += 1
+    return y

@@ -4,7 +4,7 @@ Mirrors model_executor/forward_info.py:18-66 (ForwardMode), 69-81 (CaptureHidden
 (ForwardBatch + init_new), 400-471 (positions) and scheduler/schedule_batch.py:1481-1543
 (ModelWorkerBatch) for the fields the attention hot path reads, and the log-prob request fields
 the logits processor / sampler read.  Fields that only feed out-of-scope subsystems (DP attention,
-speculative decoding, toppings, mrope) are kept as inert attributes so call sites written against the reference still construct them."""
+speculative decoding, mrope) are kept as inert attributes so call sites written against the reference still construct them."""
 import threading
 from dataclasses import dataclass
 from enum import IntEnum, auto
@@ -176,7 +176,8 @@ class ForwardBatch:
 
         Provenance: this is glue whose statement order is dictated by the field contract - which ModelWorkerBatch
         field lands in which ForwardBatch field, and what is derived when - so it follows the reference's init_new
-        assignment by assignment, minus its DP-attention buffers, mrope and toppings branches (out of scope), and
+        assignment by assignment, minus its DP-attention buffers and mrope branches (out of scope; topping_paths is read by
+        ToppingsManager.prepare_topping_batch), and
         with the two positions helpers replaced by the HIP entry points."""
         device = model_runner.device
         ret = cls(

@@ -444,7 +444,10 @@ class LlamaMLP(nn.Module):
     def forward(self, x, reduce_output: bool = True):
         # small decode steps (<= _native.SILU_FUSED_MAX_ROWS tokens): projection and activation in one weight-streaming launch, the bits of
         # the skinny projection followed by act_fn
-        act = _native.linear_silu_mul(x, self.gate_up_proj.weight)
+        # (a gate_up_proj that carries toppings opts out: its delta has to land before the activation)
+        act = None
+        if not getattr(self.gate_up_proj, "has_toppings", False):
+            act = _native.linear_silu_mul(x, self.gate_up_proj.weight)
         if act is None:
             gate_up, _ = self.gate_up_proj(x)
             act = self.act_fn(gate_up)
@@ -592,7 +595,8 @@ class LlamaForCausalLM(nn.Module):
         own = dict(self.named_parameters())
         mods = dict(self.named_modules())
         for name, param in own.items():
-            src = full[name]
+            # (a projection wrapped by a topping layer keeps its parameter under `.base_layer`: same checkpoint name)
+            src = full[name.replace(".base_layer.", ".")]
             mod = mods[name.rsplit(".", 1)[0]]
             if hasattr(mod, "shard_from_full"):
                 src = mod.shard_from_full(src)

@@ -3,8 +3,8 @@
 Mirrors the hot-path parts of model_executor/model_runner.py (init_memory_pool 360-442,
 init_attention_backend 453-470, forward/forward_decode/forward_extend 506-537, sample 539-563),
 model_executor/cuda_graph_runner.py:144-521 (static-buffer capture / padded replay) and
-managers/tp_worker.py:164-169 (forward_batch_generation).  Weight loading, offload, toppings,
-speculative decoding and the NVML/zmq control plane are out of scope.
+managers/tp_worker.py:164-169 (forward_batch_generation).  LoRA toppings: scratchpad_amd/toppings.py.  Weight
+loading, offload, speculative decoding and the NVML/zmq control plane are out of scope.
 """
 import bisect
 from dataclasses import dataclass, field
@@ -127,6 +127,11 @@ class ServerArgs:
     cuda_graph_max_bs: int = 256
     cuda_graph_bs: Optional[List[int]] = None
     kv_cache_dtype: str = "auto"
+    # toppings (args.py max_toppings_per_batch): adapter slots of the pool = adapters one batch may name; None = off
+    max_toppings_per_batch: Optional[int] = None
+    # args.py max_prefill_tokens: the most tokens one extend batch carries (the scheduler's limit, TpModelWorker); the
+    # per-token topping index buffer is sized by it
+    max_prefill_tokens: int = 16384
 
 
 def get_batch_sizes_to_capture(server_args: ServerArgs, max_reqs: int) -> List[int]:
@@ -141,9 +146,16 @@ class ModelRunner:
     def __init__(self, model_config: ModelConfig, server_args: Optional[ServerArgs] = None,
                  tp_rank: int = 0, tp_size: int = 1, device: str = "cuda",
                  dtype: torch.dtype = torch.bfloat16, gpu_id: int = 0, seed: int = 0,
-                 init_weights: bool = True):
+                 init_weights: bool = True, toppings: Optional[list] = None):
+        """``toppings``: LoRAAdapter objects (scratchpad_amd/toppings.py) to serve; with
+        ``server_args.max_toppings_per_batch`` they build the ToppingsManager, which wraps the target projections
+        (before or after the weights are loaded: ``load_full_state_dict`` / ``load_weights`` see through the wrappers).
+        One without the other is refused.  An extend batch may carry ``server_args.max_prefill_tokens`` tokens."""
         self.model_config = model_config
         self.server_args = server_args or ServerArgs()
+        if bool(toppings) != bool(self.server_args.max_toppings_per_batch):
+            raise ValueError("toppings and ServerArgs.max_toppings_per_batch go together: adapters without slots (or "
+                             "slots without adapters) would serve the base model to requests that name an adapter")
         self.tp_rank, self.tp_size = tp_rank, tp_size
         self.dtype = dtype
         # model_runner.py:360-372: "auto" = the model dtype; "fp8_e5m2" = 1-byte KV
@@ -170,6 +182,9 @@ class ModelRunner:
             maybe_attach(dist_.get_tp_group())      # opt-in (SP_CUSTOM_ALLREDUCE=1): direct IPC all-reduce
         self.sliding_window_size = None
         self.load_model(seed, init_weights)
+        self.topping_manager = None
+        if toppings:
+            self.init_toppings(toppings)
         self.init_memory_pool()
         self.init_attention_backend()
         self.graph_runner: Optional[HipGraphRunner] = None
@@ -202,6 +217,18 @@ class ModelRunner:
                     p.data.fill_(0.5)
                 else:
                     p.data.normal_(0.0, 0.02, generator=g)
+
+    def init_toppings(self, adapters):
+        """model_runner.py init_toppings: the manager is built after the model (it replaces the target modules)"""
+        from .toppings import ToppingsManager
+        if self.tp_size > 1:
+            raise NotImplementedError("toppings under tensor parallelism (TP > 1) are out of scope")
+        if self.model_config.is_encoder_decoder or self.model_config.architecture != "llama":
+            raise NotImplementedError("toppings are served on Llama only (Mllama, Qwen3 and Apertus are out of scope)")
+        max_tokens = max(self.server_args.max_prefill_tokens, self.server_args.cuda_graph_max_bs)
+        self.topping_manager = ToppingsManager(self.server_args, self.model, self.model_config, None,
+                                               adapters=adapters, device=self.device, dtype=self.dtype,
+                                               tp_size=self.tp_size, max_tokens=max_tokens)
 
     # ------------------------------------------------------------------ memory
     def profile_max_num_token(self) -> int:
@@ -281,6 +308,8 @@ class ModelRunner:
         if (forward_batch.forward_mode.is_cuda_graph() and self.graph_runner is not None
                 and self.graph_runner.can_run(forward_batch)):
             return self.graph_runner.replay(forward_batch)
+        if self.topping_manager is not None and self.topping_manager.enabled:
+            self.topping_manager.prepare_topping_batch(forward_batch)
         if forward_batch.forward_mode.is_decode():
             return self.forward_decode(forward_batch)
         if forward_batch.forward_mode.is_extend():
@@ -370,6 +399,9 @@ class HipGraphRunner:
 
     def capture(self):
         model = self.model_runner.model
+        tm = getattr(self.model_runner, "topping_manager", None)
+        if tm is not None and tm.enabled:
+            tm.weight_indices.fill_(-1)    # the captured step runs the topping kernels with every row skipped
         if self.is_encoder_decoder:
             model.capture_mode = True      # cross-attention is always part of the captured step
         try:
@@ -441,6 +473,14 @@ class HipGraphRunner:
         self.seq_lens[:raw_bs].copy_(forward_batch.seq_lens)
         self.out_cache_loc[:raw_bs].copy_(forward_batch.out_cache_loc)
         self.positions[:raw_bs].copy_(forward_batch.positions)
+        tm = self.model_runner.topping_manager
+        if tm is not None and tm.enabled:
+            # the layers hold the manager's ONE index buffer (captured by address): this batch's slots in the live
+            # rows, -1 (base model only: the row is skipped) in the padded ones.  Slot CONTENTS may have changed since
+            # the capture (an adapter loaded into a slot): the kernels read them at replay.
+            tm.prepare_topping_batch(forward_batch)
+            if bs != raw_bs:
+                tm.weight_indices[raw_bs:bs].fill_(-1)
         self.model_runner.attn_backend.init_forward_metadata_replay_cuda_graph(
             bs, self.req_pool_indices, self.seq_lens,
             forward_batch.seq_lens_sum + (bs - raw_bs) * self.seq_len_fill_value, self.encoder_lens,

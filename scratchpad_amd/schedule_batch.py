@@ -503,10 +503,9 @@ class ScheduleBatch:
         self.extend_num_tokens = 0
 
     def prepare_for_decode(self, topping_manager=None):
-        """schedule_batch.py:1230-1308.  ``topping_manager``: the reference's LoRA/delta manager; an ENABLED one
-        re-orders the batch by adapter - toppings are out of scope, so that is refused rather than ignored."""
-        if topping_manager is not None and getattr(topping_manager, "enabled", False):
-            raise NotImplementedError("toppings (LoRA / delta adapters) are out of scope of this path")
+        """schedule_batch.py:1230-1308.  ``topping_manager``: the LoRA manager (scratchpad_amd/toppings.py).  The
+        reference re-orders the batch by adapter for an enabled one, because its kernels want sorted indices; the
+        kernels here take any order (and give every row the same bits in any order), so the batch order is left alone."""
         self.forward_mode = ForwardMode.DECODE
         bs = len(self.reqs)
         self.input_ids = self.output_ids
