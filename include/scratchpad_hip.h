@@ -500,6 +500,47 @@ SP_API int sp_lora_expand(void* y, const float* tmp, const void* b, const int32_
                    int r, int n, int num_slices, int num_slots, int64_t y_stride, int64_t tmp_stride,
                    int64_t b_slot_stride, int dtype, void* stream);
 
+/* ---- Mixture of experts (additive in ABI 10): LlamaMoE.forward (nn/models/llama/llama_moe.py:98-120) as launches
+ *      whose grids depend on (num_tokens, top_k, num_experts) and the widths alone; the grouping is read from device
+ *      memory, so a captured sequence follows the routing of every replay.  T = num_tokens, K = top_k, E = num_experts.
+ * sp_moe_route:   router_logits [T, E] in `dtype` (fp32, fp16 or bf16; row stride in elements).  topk_ids int32 [T, K]:
+ *      the K largest logits of the row, largest first; among equal logits the LOWER expert index wins; NaN counts as
+ *      the largest value.  Every id written is in [0, E) whatever the logits hold.  topk_weights fp32 [T, K]: the
+ *      softmax over those K (torch.topk, then F.softmax(dtype=float).to(x.dtype), llama_moe.py:102-104), evaluated in
+ *      fp64 in k order, rounded to fp32 and then to `dtype`.  expert_offsets int32 [E + 1] and sorted_pos int32 [T K]:
+ *      the pairs t K + k ordered by expert and, within an expert, ascending - a stable counting sort, a function of
+ *      the ids alone.  Two launches.
+ * sp_moe_gate_up: h[p, :inter] = round(silu(round(x[t] . Wg[e]^T)) * round(x[t] . Wu[e]^T)) for sorted position p
+ *      = pair t K + k of expert e; w13 [E, 2 inter, hidden] gate rows first, rows contiguous.  h [T K, inter] is
+ *      indexed by SORTED POSITION.  The rounding points are those of sp_gemm_skinny followed by sp_silu_and_mul.
+ * sp_moe_down:    tmp[t K + k, :hidden] = round(round(h[p] . W2[e]^T) * topk_weights[t, k]); w2 [E, hidden, inter].
+ *      tmp [T K, hidden] is indexed by PAIR.
+ * sp_moe_combine: out[t] = the K rows of tmp of token t, added from zero in ascending expert index, rounded to `dtype`
+ *      after every addition (the reference's results[...] += expert(x) * weight sequence, llama_moe.py:111-118).
+ * Batch invariance: the bits of a token's output depend on that token's input, its routing and the weights only - not
+ *      on T, its row or how many rows an expert received (the reduction is split by its length alone).
+ * sp_moe_block_rows: sorted positions a workgroup of the two products owns.  sp_moe_max_tokens: the largest T (16384).
+ * SP_ERR_UNSUPPORTED: E == 0 or > 64; K == 0, > 8 or > E; T > sp_moe_max_tokens(); gate_up / down / combine with a
+ *      dtype other than fp16 / bf16 (route: any of the three); hidden or inter not a positive multiple of 32.
+ * SP_ERR_INVALID_ARG before any launch: a negative size, a NULL pointer, a stride below the width it spans,
+ *      x / h / tmp / out strides or expert strides not a multiple of 8 and bases not 16-byte aligned where 16-byte
+ *      vectors are read (x, w13, h, w2, tmp, out).  T == 0 is SP_OK without a launch.  Like sp_gemm_skinny these
+ *      entries sit on the decode step and do not ask the runtime whether their pointers are device memory.        */
+SP_API int sp_moe_block_rows(void);
+SP_API int sp_moe_max_tokens(void);
+SP_API int sp_moe_route(int32_t* topk_ids, float* topk_weights, int32_t* expert_offsets, int32_t* sorted_pos,
+                 const void* router_logits, int64_t num_tokens, int num_experts, int top_k, int64_t logits_stride,
+                 int dtype, void* stream);
+SP_API int sp_moe_gate_up(void* h, const void* x, const void* w13, const int32_t* expert_offsets,
+                   const int32_t* sorted_pos, int64_t num_tokens, int top_k, int num_experts, int hidden, int inter,
+                   int64_t x_stride, int64_t h_stride, int64_t w_expert_stride, int dtype, void* stream);
+SP_API int sp_moe_down(void* tmp, const void* h, const void* w2, const float* topk_weights,
+                const int32_t* expert_offsets, const int32_t* sorted_pos, int64_t num_tokens, int top_k,
+                int num_experts, int hidden, int inter, int64_t h_stride, int64_t tmp_stride,
+                int64_t w_expert_stride, int dtype, void* stream);
+SP_API int sp_moe_combine(void* out, const void* tmp, const int32_t* topk_ids, int64_t num_tokens, int top_k,
+                   int num_experts, int hidden, int64_t tmp_stride, int64_t out_stride, int dtype, void* stream);
+
 /* ---- Direct all-reduce through IPC-mapped peer regions: fills GroupCoordinator.ca_comm
  *      (distributed/parallel_state.py:266-267, 326-347; the reference never constructs one and always
  *      calls NCCL, linear.py:1148-1149).  Each rank sp_ar_alloc()s one fine-grained region of

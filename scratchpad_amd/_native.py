@@ -114,6 +114,12 @@ SIGNATURES = {
     "sp_gemm_skinny_xielu": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _i32, _vp]),
     "sp_lora_shrink": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
     "sp_lora_expand": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "sp_moe_block_rows": (_i32, []),
+    "sp_moe_max_tokens": (_i32, []),
+    "sp_moe_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _vp]),
+    "sp_moe_gate_up": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "sp_moe_down": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "sp_moe_combine": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _vp]),
 }
 
 
@@ -1282,3 +1288,131 @@ def lora_expand(y: torch.Tensor, tmp: torch.Tensor, B: torch.Tensor, indices: to
            "sp_lora_expand")
     LORA_CALLS["expand"] += 1
     return y
+
+
+# --------------------------------------------------------------------------- mixture of experts
+# launches by entry ("route" counts one sp_moe_route call: two launches), and "fallback" = one run of the per-expert
+# library loop (moe_experts_eager: fp32 models and the bench baseline).  Tests prove with it which path a step took.
+MOE_CALLS = {"route": 0, "gate_up": 0, "down": 0, "combine": 0, "fallback": 0}
+MOE_MAX_EXPERTS = 64
+MOE_MAX_TOP_K = 8
+MOE_MAX_TOKENS = 16384          # sp_moe_max_tokens()
+MOE_BLOCK_ROWS = 32             # sp_moe_block_rows(): sorted positions one workgroup of the two products owns
+
+
+def moe_block_rows() -> int:
+    """the library's own figure (tests build their row counts around it)"""
+    return int(load().sp_moe_block_rows())
+
+
+def moe_route(router_logits: torch.Tensor, top_k: int):
+    """sp_moe_route: router_logits [T, E] (fp32 / fp16 / bf16, contiguous columns, any row stride) ->
+    (topk_ids int32 [T, K], topk_weights fp32 [T, K], expert_offsets int32 [E + 1], sorted_pos int32 [T K])."""
+    _gpu(router_logits)
+    if router_logits.dim() != 2 or (router_logits.shape[1] > 1 and router_logits.stride(1) != 1):
+        raise RuntimeError("moe_route: router_logits must be [T, E] with contiguous columns")
+    T, E = router_logits.shape
+    K = int(top_k)
+    dev = router_logits.device
+    ids = torch.empty((T, K), dtype=torch.int32, device=dev)
+    wts = torch.empty((T, K), dtype=torch.float32, device=dev)
+    offsets = torch.empty((E + 1,), dtype=torch.int32, device=dev)
+    pos = torch.empty((T * K,), dtype=torch.int32, device=dev)
+    if T == 0:
+        return ids, wts, offsets.zero_(), pos
+    _check(load().sp_moe_route(ids.data_ptr(), wts.data_ptr(), offsets.data_ptr(), pos.data_ptr(),
+                               router_logits.data_ptr(), T, E, K, router_logits.stride(0), _dt(router_logits),
+                               _stream()), "sp_moe_route")
+    MOE_CALLS["route"] += 1
+    return ids, wts, offsets, pos
+
+
+def _moe_stacked(w: torch.Tensor, rows: int, cols: int, what: str) -> None:
+    if w.dim() != 3 or w.shape[1] != rows or w.shape[2] != cols or w.stride(2) != 1 or w.stride(1) != cols:
+        raise RuntimeError(f"{what}: stacked expert weight must be [E, {rows}, {cols}] with contiguous [rows, cols] "
+                           f"slots, got {tuple(w.shape)} strides {tuple(w.stride())}")
+
+
+def moe_gate_up(x: torch.Tensor, w13: torch.Tensor, expert_offsets: torch.Tensor, sorted_pos: torch.Tensor,
+                top_k: int) -> torch.Tensor:
+    """sp_moe_gate_up: x [T, H], w13 [E, 2 I, H] (gate rows first) -> h [T K, I] by sorted position (rows at or past
+    expert_offsets[E] are left uninitialised: nothing reads them)."""
+    _gpu(x, w13, expert_offsets, sorted_pos)
+    if x.dim() != 2 or x.stride(1) != 1 or w13.dtype != x.dtype or w13.dim() != 3 or w13.shape[1] % 2:
+        raise RuntimeError("moe_gate_up: x [T, H] row-contiguous and w13 [E, 2 I, H] of one dtype")
+    T, H = x.shape
+    E, inter = w13.shape[0], w13.shape[1] // 2
+    _moe_stacked(w13, 2 * inter, H, "moe_gate_up")
+    h = torch.empty((T * top_k, inter), dtype=x.dtype, device=x.device)
+    if T == 0:
+        return h
+    _check(load().sp_moe_gate_up(h.data_ptr(), x.data_ptr(), w13.data_ptr(), expert_offsets.data_ptr(),
+                                 sorted_pos.data_ptr(), T, int(top_k), E, H, inter, x.stride(0), h.stride(0),
+                                 w13.stride(0), _dt(x), _stream()), "sp_moe_gate_up")
+    MOE_CALLS["gate_up"] += 1
+    return h
+
+
+def moe_down(h: torch.Tensor, w2: torch.Tensor, topk_weights: torch.Tensor, expert_offsets: torch.Tensor,
+             sorted_pos: torch.Tensor, top_k: int) -> torch.Tensor:
+    """sp_moe_down: h [T K, I] by sorted position, w2 [E, H, I] -> tmp [T K, H] by pair, scaled by the pair's weight"""
+    _gpu(h, w2, topk_weights, expert_offsets, sorted_pos)
+    if h.dim() != 2 or h.stride(1) != 1 or w2.dtype != h.dtype or w2.dim() != 3 or h.shape[0] % top_k \
+            or topk_weights.dtype != torch.float32 or not topk_weights.is_contiguous():
+        raise RuntimeError("moe_down: h [T K, I] row-contiguous, w2 [E, H, I] of its dtype, contiguous fp32 weights")
+    NP, inter = h.shape
+    E, H = w2.shape[0], w2.shape[1]
+    _moe_stacked(w2, H, inter, "moe_down")
+    tmp = torch.empty((NP, H), dtype=h.dtype, device=h.device)
+    if NP == 0:
+        return tmp
+    _check(load().sp_moe_down(tmp.data_ptr(), h.data_ptr(), w2.data_ptr(), topk_weights.data_ptr(),
+                              expert_offsets.data_ptr(), sorted_pos.data_ptr(), NP // top_k, int(top_k), E, H, inter,
+                              h.stride(0), tmp.stride(0), w2.stride(0), _dt(h), _stream()), "sp_moe_down")
+    MOE_CALLS["down"] += 1
+    return tmp
+
+
+def moe_combine(tmp: torch.Tensor, topk_ids: torch.Tensor, num_experts: int) -> torch.Tensor:
+    """sp_moe_combine: tmp [T K, H] by pair, topk_ids int32 [T, K] -> out [T, H]"""
+    _gpu(tmp, topk_ids)
+    if tmp.dim() != 2 or tmp.stride(1) != 1 or topk_ids.dtype != torch.int32 or not topk_ids.is_contiguous() \
+            or topk_ids.dim() != 2 or tmp.shape[0] != topk_ids.numel():
+        raise RuntimeError("moe_combine: tmp [T K, H] row-contiguous and contiguous int32 topk_ids [T, K]")
+    T, K = topk_ids.shape
+    out = empty_rows(T, tmp.shape[1], tmp.dtype, tmp.device)
+    if T == 0:
+        return out
+    _check(load().sp_moe_combine(out.data_ptr(), tmp.data_ptr(), topk_ids.data_ptr(), T, K, int(num_experts),
+                                 tmp.shape[1], tmp.stride(0), out.stride(0), _dt(tmp), _stream()), "sp_moe_combine")
+    MOE_CALLS["combine"] += 1
+    return out
+
+
+def moe_experts(x: torch.Tensor, router_logits: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
+                top_k: int) -> torch.Tensor:
+    """The fused MoE layer behind the router projection: five launches whatever the routing (graph-capturable)."""
+    ids, wts, offsets, pos = moe_route(router_logits, top_k)
+    h = moe_gate_up(x, w13, offsets, pos, top_k)
+    tmp = moe_down(h, w2, wts, offsets, pos, top_k)
+    return moe_combine(tmp, ids, w13.shape[0])
+
+
+def moe_experts_eager(x: torch.Tensor, router_logits: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
+                      top_k: int) -> torch.Tensor:
+    """The reference's formulation behind sp_moe_route: one library product per expert over its gathered rows, added
+    in ascending expert index in x's dtype (llama_moe.py:105-118).  Row counts come to the host: eager only."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("moe_experts_eager synchronises with the host (per-expert row counts): it cannot be "
+                           "captured into a graph; fp32 MoE models run eagerly")
+    ids, wts, _offsets, _pos = moe_route(router_logits, top_k)
+    wts = wts.to(x.dtype)
+    out = torch.zeros_like(x)
+    for e in range(w13.shape[0]):
+        tok, k = torch.where(ids == e)
+        if tok.numel() == 0:
+            continue
+        act = silu_and_mul(linear(x[tok], w13[e]))
+        out[tok] += linear(act, w2[e]) * wts[tok, k].unsqueeze(-1)
+    MOE_CALLS["fallback"] += 1
+    return out

@@ -43,9 +43,14 @@ class ModelConfig:
     pad_token_id: Optional[int] = None
     # Mllama: the vision tower's config (MllamaVisionConfig fields); None = text side only
     vision_config: Optional[object] = None
-    # which decoder load_model builds: "llama" (with cross_attention_layers: Mllama), "qwen3" or "apertus"
+    # which decoder load_model builds: "llama" (with cross_attention_layers: Mllama), "qwen3", "apertus" or
+    # "llama_moe"
     architecture: str = "llama"
     attention_bias: bool = False        # Qwen3: refused when set (scratchpad_amd/qwen3.py)
+    # Llama-MoE (scratchpad_amd/llama_moe.py): experts per layer and experts a token is routed to
+    num_experts: Optional[int] = None
+    experts_per_token: Optional[int] = None
+    grouped_topk: bool = False          # refused when set: plain top-k routing only
 
     @property
     def is_encoder_decoder(self) -> bool:
@@ -54,8 +59,19 @@ class ModelConfig:
     def __post_init__(self):
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
-        if self.architecture not in ("llama", "qwen3", "apertus"):
-            raise ValueError(f"Unsupported architecture: {self.architecture!r} (llama, qwen3, apertus)")
+        if self.architecture in ("llama_quant_moe", "llama_naive_quant_moe"):
+            raise NotImplementedError(f"architecture {self.architecture!r}: the quantised MoE models are out of scope "
+                                      "(llama_moe is the one that is built)")
+        if self.architecture not in ("llama", "qwen3", "apertus", "llama_moe"):
+            raise ValueError(f"Unsupported architecture: {self.architecture!r} (llama, qwen3, apertus, llama_moe)")
+        if self.architecture == "llama_moe":
+            if self.grouped_topk:
+                raise NotImplementedError("grouped_topk is not built: plain top-k routing only")
+            if not self.num_experts or not self.experts_per_token:
+                raise ValueError("architecture 'llama_moe' needs num_experts and experts_per_token")
+            if self.num_experts > 64 or not 0 < self.experts_per_token <= min(self.num_experts, 8):
+                raise NotImplementedError(f"num_experts={self.num_experts}, experts_per_token="
+                                          f"{self.experts_per_token}: at most 64 experts and top-8 are built")
 
     def get_num_kv_heads(self, tp_size: int) -> int:
         # model_config.py:155-163: replicate KV heads when tp > total_kv
@@ -113,6 +129,14 @@ class ModelConfig:
                    rope_scaling={"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0,
                                  "high_freq_factor": 4.0, "original_max_position_embeddings": 8192},
                    max_position_embeddings=max(65536, context_len), hidden_act="xielu", architecture="apertus")
+
+    @classmethod
+    def llama_moe_8x7b(cls, context_len: int = 8192):
+        """The widths published for Mixtral-8x7B under the reference's Llama-MoE layout: 8 experts, top-2.  The
+        figures are written from memory of the released configuration and are NOT verified against it."""
+        return cls(4096, 14336, 32, 32, 8, 32000, context_len=context_len, rms_norm_eps=1e-5, rope_theta=1000000.0,
+                   max_position_embeddings=max(32768, context_len), architecture="llama_moe", num_experts=8,
+                   experts_per_token=2)
 
 
 @dataclass
@@ -201,6 +225,11 @@ class ModelRunner:
             elif self.model_config.architecture == "apertus":
                 from .apertus import SwissAIForCausalLM
                 self.model = SwissAIForCausalLM(self.model_config, dtype=self.dtype).eval()
+            elif self.model_config.architecture == "llama_moe":
+                if self.tp_size > 1:
+                    raise NotImplementedError("Llama-MoE under tensor parallelism (TP > 1) is out of scope")
+                from .llama_moe import LlamaMoEForCausalLM
+                self.model = LlamaMoEForCausalLM(self.model_config, dtype=self.dtype).eval()
             else:
                 self.model = LlamaForCausalLM(self.model_config, dtype=self.dtype).eval()
         for p in self.model.parameters():
@@ -224,7 +253,8 @@ class ModelRunner:
         if self.tp_size > 1:
             raise NotImplementedError("toppings under tensor parallelism (TP > 1) are out of scope")
         if self.model_config.is_encoder_decoder or self.model_config.architecture != "llama":
-            raise NotImplementedError("toppings are served on Llama only (Mllama, Qwen3 and Apertus are out of scope)")
+            raise NotImplementedError("toppings are served on Llama only (Mllama, Qwen3, Apertus and Llama-MoE are out "
+                                      "of scope)")
         max_tokens = max(self.server_args.max_prefill_tokens, self.server_args.cuda_graph_max_bs)
         self.topping_manager = ToppingsManager(self.server_args, self.model, self.model_config, None,
                                                adapters=adapters, device=self.device, dtype=self.dtype,
