@@ -541,6 +541,34 @@ SP_API int sp_moe_down(void* tmp, const void* h, const void* w2, const float* to
 SP_API int sp_moe_combine(void* out, const void* tmp, const int32_t* topk_ids, int64_t num_tokens, int top_k,
                    int num_experts, int hidden, int64_t tmp_stride, int64_t out_stride, int dtype, void* stream);
 
+/* ---- Embedding requests (additive in ABI 10): the final norm of the decoder, Pooler(PoolingType.LAST) and
+ *      F.normalize (nn/layers/pooler.py:38-50 behind nn/models/llama/llama.py:268) in one launch, on the num_seqs
+ *      rows that matter.  One workgroup per sequence i:
+ *        row_i  = extend_seq_lens[0] + ... + extend_seq_lens[i] - 1        (int32 lengths, int64 with idx64)
+ *        n      = weight ? the row sp_fused_add_rmsnorm (residual given) / sp_rmsnorm (residual NULL) writes for
+ *                          row_i, bit for bit : x[row_i]
+ *        out[i] = normalize ? round(n / max(round(||n||_2), round(1e-12))) : n
+ *      ("bit for bit": the norm entries sum the squares in one of two orders, chosen by whether base, stride and
+ *      width of x, residual, weight AND of the buffer they write allow 16-byte accesses.  This entry chooses by x,
+ *      residual and weight alone - its `out` is no counterpart of theirs - so it matches sp_fused_add_rmsnorm, which
+ *      writes x itself, always, and sp_rmsnorm whenever that call's own `out` is 16-byte aligned with an out_stride
+ *      that is a multiple of 16 bytes, or x already forces element accesses.)
+ *      ||n||_2 is accumulated in fp32 in an order fixed by `hidden` alone, so a sequence's bits do not depend on
+ *      num_seqs, on i or on the other rows; round() rounds to `dtype` (fp16: round(1e-12) = 0, an all-zero row gives
+ *      NaN as torch's F.normalize does; a norm beyond the fp16 range gives zeros).  x and residual are NOT written.
+ *      A sequence of length <= 0, or a row_i outside [0, num_tokens), forms no address: out[i] is zeros.
+ *      Only row i itself is refused: the lengths are not validated as a whole, so a NEGATIVE length moves row_j of
+ *      every later sequence j down without any warning, and those rows are then pooled from the wrong tokens (a zero
+ *      length moves nothing).  Every workgroup adds extend_seq_lens[0..i] itself - num_seqs^2 / 2 index reads per
+ *      launch in all, which is nothing at serving batch sizes and would want a prefix pass at tens of thousands.
+ *      Any hidden; 16-byte accesses where base, stride and width allow, element accesses otherwise.  Strides in
+ *      elements.  num_seqs == 0 is SP_OK without a launch.  SP_ERR_INVALID_ARG before any launch: out, x or
+ *      extend_seq_lens NULL, a negative size, hidden <= 0, a stride below hidden, residual without weight, weight
+ *      with eps <= 0.  SP_ERR_UNSUPPORTED: a dtype other than fp32 / fp16 / bf16.                                  */
+SP_API int sp_embedding_pool(void* out, int64_t out_stride, const void* x, int64_t x_stride, const void* residual,
+                      int64_t res_stride, const void* weight, float eps, const void* extend_seq_lens, int idx64,
+                      int num_seqs, int64_t num_tokens, int hidden, int normalize, int dtype, void* stream);
+
 /* ---- Direct all-reduce through IPC-mapped peer regions: fills GroupCoordinator.ca_comm
  *      (distributed/parallel_state.py:266-267, 326-347; the reference never constructs one and always
  *      calls NCCL, linear.py:1148-1149).  Each rank sp_ar_alloc()s one fine-grained region of

@@ -120,6 +120,8 @@ SIGNATURES = {
     "sp_moe_gate_up": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "sp_moe_down": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "sp_moe_combine": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _vp]),
+    "sp_embedding_pool": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _f32, _vp, _i32, _i32, _i64, _i32, _i32, _i32,
+                                 _vp]),
 }
 
 
@@ -225,6 +227,51 @@ def fused_add_rmsnorm(x: torch.Tensor, residual: torch.Tensor, weight: torch.Ten
     _check(load().sp_fused_add_rmsnorm(x.data_ptr(), residual.data_ptr(), w.data_ptr(), x.shape[0],
                                        x.shape[1], x.stride(0), residual.stride(0), eps, _dt(x),
                                        _stream()), "sp_fused_add_rmsnorm")
+
+
+# calls of embedding_pool by the form they took: "fused" = the final norm, the last-token gather and the L2 step in one
+# launch (a norm weight was given), "gather" = gather (+ L2) of rows that are already normed
+EMBEDDING_CALLS = {"fused": 0, "gather": 0}
+
+
+def embedding_pool(hidden_states: torch.Tensor, extend_seq_lens: torch.Tensor, normalize: bool = True,
+                   residual: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
+                   eps: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pooler(PoolingType.LAST, normalize) (pooler.py:38-50) over hidden_states [T, H]: row cumsum(extend_seq_lens) - 1
+    of every sequence, L2-normalised at F.normalize's rounding points -> [B, H] in hidden_states' dtype, one launch
+    (sp_embedding_pool).  With ``weight`` (and ``eps``) the rows first get the bits RMSNorm(weight)(hidden_states,
+    residual) would give them - the decoder's final norm on B rows instead of T.  hidden_states and residual are
+    read only.  A sequence without tokens, or lengths that leave [0, T), give a row of zeros."""
+    _gpu(hidden_states, extend_seq_lens, residual, weight, out)
+    x = hidden_states
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise RuntimeError("embedding_pool needs 2-D row-contiguous hidden_states")
+    if residual is not None:
+        if weight is None:
+            raise RuntimeError("embedding_pool: a residual goes with a norm weight")
+        if residual.shape != x.shape or residual.dtype != x.dtype or residual.stride(1) != 1:
+            raise RuntimeError("embedding_pool: residual must have hidden_states' shape, dtype and contiguous rows")
+    if extend_seq_lens.dtype not in (torch.int32, torch.int64) or extend_seq_lens.dim() != 1:
+        raise RuntimeError("embedding_pool: extend_seq_lens must be a 1-D int32 / int64 tensor")
+    lens = extend_seq_lens.contiguous()
+    B, H = lens.shape[0], x.shape[1]
+    if out is None:
+        out = torch.empty((B, H), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.dim() != 2 or out.shape != (B, H) or out.stride(1) != 1:
+        raise RuntimeError("embedding_pool: out must be [num_seqs, hidden], row-contiguous, of hidden_states' dtype")
+    w = None
+    if weight is not None:
+        if weight.shape != (H,):
+            raise RuntimeError(f"embedding_pool: the norm weight must be [{H}]")
+        w = (weight if weight.dtype == x.dtype else weight.to(x.dtype)).contiguous()
+    if B == 0:
+        return out
+    _check(load().sp_embedding_pool(out.data_ptr(), out.stride(0), x.data_ptr(), x.stride(0), _ptr(residual),
+                                    0 if residual is None else residual.stride(0), _ptr(w), float(eps),
+                                    lens.data_ptr(), int(lens.dtype == torch.int64), B, x.shape[0], H,
+                                    int(bool(normalize)), _dt(x), _stream()), "sp_embedding_pool")
+    EMBEDDING_CALLS["fused" if w is not None else "gather"] += 1
+    return out
 
 
 def silu_and_mul(x: torch.Tensor) -> torch.Tensor:

@@ -16,6 +16,9 @@ namespace sp {
 
 static constexpr int kBlock = 256;
 
+// The order of this sum and of wave_sum (sp_common.h) - six butterfly steps, then the four waves added in turn - is
+// what the error bound of the embedding-pool tests counts on (`sum_depth` in the tests' error model: 6 + 4 additions
+// behind a lane's own): change them together.
 __device__ __forceinline__ float block_sum(float v, float* smem) {
   v = wave_sum(v);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -32,6 +35,57 @@ __device__ __forceinline__ float block_sum(float v, float* smem) {
 // nn/layers/layernorm.py:34-51.  y = round(xf * rsqrt(mean(xf^2)+eps)) * w  (second product
 // rounded again: torch multiplies two `dtype` tensors).  Fused: xf = x + residual in fp32,
 // residual <- round(xf), and the UNROUNDED xf is normalised.
+//
+// The row routine, shared by the norm kernels and embedding_pool_kernel (which must give the norm kernels' bits):
+// rmsnorm_load_vec / row_elem read a row (and add the residual), rmsnorm_rs reduces the lanes' partial sums of
+// squares to 1 / sqrt(mean + eps), rmsnorm_elem holds the two rounding points of an output element.
+
+// x[i] (+ residual[i] in fp32): the value the norm is taken of
+template <typename Tag, bool FUSED>
+__device__ __forceinline__ float row_elem(const void* x, const void* residual, int64_t xi, int64_t ri) {
+  typedef Elem<Tag> E;
+  float v = E::load(x, xi);
+  if (FUSED) v = __fadd_rn(v, E::load(residual, ri));
+  return v;
+}
+
+// 16-byte path: lane t keeps vectors t, t + kBlock, ... of the row in `cache` (fp32) and returns the sum of their
+// squares, added in element order.  WRITE_RES: residual <- round(x + residual), as sp_fused_add_rmsnorm does.
+template <typename Tag, bool FUSED, bool WRITE_RES, int MAXIT>
+__device__ __forceinline__ float rmsnorm_load_vec(const char* xrow, char* rrow, int nvec,
+                                                  float (&cache)[MAXIT][Elem<Tag>::kVec]) {
+  constexpr int V = Elem<Tag>::kVec;
+  float ss = 0.f;
+#pragma unroll
+  for (int it = 0; it < MAXIT; ++it) {
+    const int v = threadIdx.x + it * kBlock;
+    if (v < nvec) {
+      unpack16<Tag>(ld16(xrow + (int64_t)v * 16), cache[it]);
+      if (FUSED) {
+        float r[V];
+        unpack16<Tag>(ld16(rrow + (int64_t)v * 16), r);
+#pragma unroll
+        for (int e = 0; e < V; ++e) cache[it][e] = __fadd_rn(cache[it][e], r[e]);
+        if (WRITE_RES) st16(rrow + (int64_t)v * 16, pack16<Tag>(cache[it]));
+      }
+#pragma unroll
+      for (int e = 0; e < V; ++e) ss += cache[it][e] * cache[it][e];
+    }
+  }
+  return ss;
+}
+
+__device__ __forceinline__ float rmsnorm_rs(float ss, float* smem, int hidden, float eps) {
+  const float mean = block_sum(ss, smem) / (float)hidden;
+  return 1.0f / sqrtf(mean + eps);
+}
+
+// one output element, before the store rounds it
+template <typename Tag>
+__device__ __forceinline__ float rmsnorm_elem(float v, float rs, float w) {
+  return __fmul_rn(Elem<Tag>::round(__fmul_rn(v, rs)), w);
+}
+
 template <typename Tag, bool FUSED, int MAXIT>
 __global__ __launch_bounds__(kBlock) void rmsnorm_vec_kernel(void* out,  // may alias x_io (fused)
                                                               void* x_io, void* residual,
@@ -48,25 +102,8 @@ __global__ __launch_bounds__(kBlock) void rmsnorm_vec_kernel(void* out,  // may 
   char* orow = (char*)out + row * o_stride * E::kBytes;
   const int nvec = hidden / V;
   float cache[MAXIT][V];
-  float ss = 0.f;
-#pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
-    const int v = threadIdx.x + it * kBlock;
-    if (v < nvec) {
-      unpack16<Tag>(ld16(xrow + (int64_t)v * 16), cache[it]);
-      if (FUSED) {
-        float r[V];
-        unpack16<Tag>(ld16(rrow + (int64_t)v * 16), r);
-#pragma unroll
-        for (int e = 0; e < V; ++e) cache[it][e] = __fadd_rn(cache[it][e], r[e]);
-        st16(rrow + (int64_t)v * 16, pack16<Tag>(cache[it]));
-      }
-#pragma unroll
-      for (int e = 0; e < V; ++e) ss += cache[it][e] * cache[it][e];
-    }
-  }
-  const float mean = block_sum(ss, smem) / (float)hidden;
-  const float rs = 1.0f / sqrtf(mean + eps);
+  const float ss = rmsnorm_load_vec<Tag, FUSED, true, MAXIT>(xrow, rrow, nvec, cache);
+  const float rs = rmsnorm_rs(ss, smem, hidden, eps);
 #pragma unroll
   for (int it = 0; it < MAXIT; ++it) {
     const int v = threadIdx.x + it * kBlock;
@@ -74,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void rmsnorm_vec_kernel(void* out,  // may 
       float w[V], y[V];
       unpack16<Tag>(ld16((const char*)weight + (int64_t)v * 16), w);
 #pragma unroll
-      for (int e = 0; e < V; ++e) y[e] = __fmul_rn(E::round(__fmul_rn(cache[it][e], rs)), w[e]);
+      for (int e = 0; e < V; ++e) y[e] = rmsnorm_elem<Tag>(cache[it][e], rs, w[e]);
       st16(orow + (int64_t)v * 16, pack16<Tag>(y));
     }
   }
@@ -93,21 +130,15 @@ __global__ __launch_bounds__(kBlock) void rmsnorm_scalar_kernel(void* out,  // m
   const int64_t row = blockIdx.x;
   float ss = 0.f;
   for (int i = threadIdx.x; i < hidden; i += kBlock) {
-    float v = E::load(x_io, row * x_stride + i);
     // pass two recomputes the fp32 sum from x and the OLD residual, so nothing is written yet
-    if (FUSED) v = __fadd_rn(v, E::load(residual, row * r_stride + i));
+    const float v = row_elem<Tag, FUSED>(x_io, residual, row * x_stride + i, row * r_stride + i);
     ss += v * v;
   }
-  const float mean = block_sum(ss, smem) / (float)hidden;
-  const float rs = 1.0f / sqrtf(mean + eps);
+  const float rs = rmsnorm_rs(ss, smem, hidden, eps);
   for (int i = threadIdx.x; i < hidden; i += kBlock) {
-    float v = E::load(x_io, row * x_stride + i);
-    if (FUSED) {
-      v = __fadd_rn(v, E::load(residual, row * r_stride + i));
-      E::store(residual, row * r_stride + i, v);
-    }
-    const float w = E::load(weight, i);
-    E::store(out, row * o_stride + i, __fmul_rn(E::round(__fmul_rn(v, rs)), w));
+    const float v = row_elem<Tag, FUSED>(x_io, residual, row * x_stride + i, row * r_stride + i);
+    if (FUSED) E::store(residual, row * r_stride + i, v);
+    E::store(out, row * o_stride + i, rmsnorm_elem<Tag>(v, rs, E::load(weight, i)));
   }
 }
 
@@ -608,6 +639,154 @@ __global__ void clamp_position_kernel(int64_t* __restrict__ positions,
   }
 }
 
+// ------------------------------------------------------------- embedding: pool + norm + L2
+// nn/layers/pooler.py:38-50 behind the final norm of the decoder (nn/models/llama/llama.py:268): one workgroup per
+// sequence takes the LAST row of that sequence, gives it the bits sp_fused_add_rmsnorm / sp_rmsnorm would (the row
+// routine above, the same path choice and summation order) and divides it by its 2-norm at F.normalize's rounding
+// points: the norm accumulated in fp32 and rounded to `dtype`, clamped below at 1e-12 as `dtype` holds it (0 in
+// fp16), each quotient taken in fp32 and rounded once.  x and residual are read only.
+// The sum of squares of the L2 step: lane t adds elements [c V, c V + V) of chunks c = t, t + kBlock, ... in
+// ascending order, block_sum folds the lanes - an order fixed by `hidden` alone, the same on both paths, and the one
+// the error bound of its tests assumes (`sum_depth`: V ceil(ceil(hidden / V) / kBlock) + 10 additions).
+struct EmbedArgs {
+  void* out;
+  const void* x;
+  const void* residual;
+  const void* weight;
+  const void* lens;
+  int64_t o_stride, x_stride, r_stride, num_tokens;
+  int hidden, idx64, normalize, out_vec;
+  float eps;
+};
+
+// row of x this workgroup pools, or -1: a sequence without tokens, or lengths that leave [0, num_tokens)
+__device__ __forceinline__ int64_t embedding_row(const EmbedArgs& a, int64_t* smem) {
+  const int i = blockIdx.x;
+  const int64_t end = block_prefix_i64(a.idx64 ? (const int64_t*)a.lens : nullptr,
+                                       a.idx64 ? nullptr : (const int32_t*)a.lens, i + 1, smem);
+  const int64_t row = end - 1;
+  return (load_idx(a.lens, i, a.idx64) > 0 && row >= 0 && row < a.num_tokens) ? row : -1;
+}
+
+template <typename Tag>
+__device__ __forceinline__ void embedding_zero_row(const EmbedArgs& a) {
+  for (int i = threadIdx.x; i < a.hidden; i += kBlock)
+    Elem<Tag>::store(a.out, (int64_t)blockIdx.x * a.o_stride + i, 0.f);
+}
+
+// max(round(sqrt(sum n^2)), round(1e-12)); a NaN norm stays NaN, as torch.clamp_min leaves it
+template <typename Tag>
+__device__ __forceinline__ float l2_denominator(float ss, float* smem) {
+  typedef Elem<Tag> E;
+  const float norm = E::round(__fsqrt_rn(block_sum(ss, smem)));
+  const float lo = E::round(1e-12f);
+  return norm < lo ? lo : norm;
+}
+
+template <typename Tag, bool FUSED, int MAXIT>
+__global__ __launch_bounds__(kBlock) void embedding_pool_vec_kernel(EmbedArgs a) {
+  typedef Elem<Tag> E;
+  constexpr int V = E::kVec;
+  __shared__ float smem[kBlock / 64];
+  __shared__ int64_t ismem[kBlock / 64];
+  const int64_t row = embedding_row(a, ismem);
+  if (row < 0) {                                   // the same for every lane of the workgroup
+    embedding_zero_row<Tag>(a);
+    return;
+  }
+  const char* xrow = (const char*)a.x + row * a.x_stride * E::kBytes;
+  char* rrow = FUSED ? (char*)a.residual + row * a.r_stride * E::kBytes : nullptr;   // read only (WRITE_RES off)
+  const int nvec = a.hidden / V;
+  float cache[MAXIT][V];
+  const float ss = rmsnorm_load_vec<Tag, FUSED, false, MAXIT>(xrow, rrow, nvec, cache);
+  float ss2 = 0.f;
+  if (a.weight) {                                  // uniform
+    const float rs = rmsnorm_rs(ss, smem, a.hidden, a.eps);
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) {
+      const int v = threadIdx.x + it * kBlock;
+      if (v < nvec) {
+        float w[V];
+        unpack16<Tag>(ld16((const char*)a.weight + (int64_t)v * 16), w);
+#pragma unroll
+        for (int e = 0; e < V; ++e) cache[it][e] = E::round(rmsnorm_elem<Tag>(cache[it][e], rs, w[e]));
+      }
+    }
+  }
+  if (a.normalize) {
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) {
+      if (threadIdx.x + it * kBlock < nvec) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) ss2 += cache[it][e] * cache[it][e];
+      }
+    }
+    const float denom = l2_denominator<Tag>(ss2, smem);
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) {
+      if (threadIdx.x + it * kBlock < nvec) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) cache[it][e] = __fdiv_rn(cache[it][e], denom);
+      }
+    }
+  }
+  const int64_t obase = (int64_t)blockIdx.x * a.o_stride;
+#pragma unroll
+  for (int it = 0; it < MAXIT; ++it) {
+    const int v = threadIdx.x + it * kBlock;
+    if (v < nvec) {
+      if (a.out_vec) {
+        st16((char*)a.out + (obase + (int64_t)v * V) * E::kBytes, pack16<Tag>(cache[it]));
+      } else {
+#pragma unroll
+        for (int e = 0; e < V; ++e) E::store(a.out, obase + (int64_t)v * V + e, cache[it][e]);
+      }
+    }
+  }
+}
+
+// any hidden / stride / alignment: the norm step in rmsnorm_scalar_kernel's two passes and order; the row is parked in
+// `out` (every lane re-reads only what it wrote itself) while its sum of squares is reduced
+template <typename Tag, bool FUSED>
+__global__ __launch_bounds__(kBlock) void embedding_pool_scalar_kernel(EmbedArgs a) {
+  typedef Elem<Tag> E;
+  constexpr int V = E::kVec;
+  __shared__ float smem[kBlock / 64];
+  __shared__ int64_t ismem[kBlock / 64];
+  const int64_t row = embedding_row(a, ismem);
+  if (row < 0) {
+    embedding_zero_row<Tag>(a);
+    return;
+  }
+  const int64_t xb = row * a.x_stride, rb = row * a.r_stride, ob = (int64_t)blockIdx.x * a.o_stride;
+  float rs = 0.f;
+  if (a.weight) {
+    float ss = 0.f;
+    for (int i = threadIdx.x; i < a.hidden; i += kBlock) {
+      const float v = row_elem<Tag, FUSED>(a.x, a.residual, xb + i, rb + i);
+      ss += v * v;
+    }
+    rs = rmsnorm_rs(ss, smem, a.hidden, a.eps);
+  }
+  float ss2 = 0.f;
+  for (int c = threadIdx.x; (int64_t)c * V < a.hidden; c += kBlock) {
+    const int hi = min(a.hidden, (c + 1) * V);
+    for (int i = c * V; i < hi; ++i) {
+      float n = row_elem<Tag, FUSED>(a.x, a.residual, xb + i, rb + i);
+      if (a.weight) n = rmsnorm_elem<Tag>(n, rs, E::load(a.weight, i));
+      n = E::round(n);
+      E::store(a.out, ob + i, n);
+      ss2 += n * n;
+    }
+  }
+  if (!a.normalize) return;
+  const float denom = l2_denominator<Tag>(ss2, smem);
+  for (int c = threadIdx.x; (int64_t)c * V < a.hidden; c += kBlock) {
+    const int hi = min(a.hidden, (c + 1) * V);
+    for (int i = c * V; i < hi; ++i) E::store(a.out, ob + i, __fdiv_rn(E::load(a.out, ob + i), denom));
+  }
+}
+
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace sp
@@ -669,6 +848,50 @@ extern "C" int sp_fused_add_rmsnorm(void* x, void* residual, const void* weight,
                                                               hidden, x_stride, res_stride,
                                                               x_stride, eps,
                                                               (hipStream_t)stream)));
+}
+
+template <typename Tag>
+static int launch_embedding_pool(EmbedArgs a, int num_seqs, hipStream_t st) {
+  typedef Elem<Tag> E;
+  constexpr int V = E::kVec;
+  constexpr int MAXIT = (E::kBytes == 4) ? 8 : 4;
+  const bool fused = a.residual != nullptr;
+  // launch_rmsnorm's rule on x, residual and weight, so that the sums of squares run in the order the norm entries
+  // use on the same inputs.  launch_rmsnorm also asks its `out` for 16 bytes: for sp_fused_add_rmsnorm that is x
+  // again; sp_rmsnorm's separate out has no counterpart here, so the match with sp_rmsnorm holds for a call of it
+  // whose out allows the 16-byte path (see the header).  This entry's own out only picks how rows are stored.
+  const bool vec = a.hidden % V == 0 && a.x_stride % V == 0 && aligned16(a.x) && (!a.weight || aligned16(a.weight)) &&
+                   (!fused || (a.r_stride % V == 0 && aligned16(a.residual))) && a.hidden / V <= kBlock * MAXIT;
+  a.out_vec = a.o_stride % V == 0 && aligned16(a.out);
+  const dim3 grid((unsigned)num_seqs);
+  if (vec) {
+    if (fused) embedding_pool_vec_kernel<Tag, true, MAXIT><<<grid, kBlock, 0, st>>>(a);
+    else embedding_pool_vec_kernel<Tag, false, MAXIT><<<grid, kBlock, 0, st>>>(a);
+  } else {
+    if (fused) embedding_pool_scalar_kernel<Tag, true><<<grid, kBlock, 0, st>>>(a);
+    else embedding_pool_scalar_kernel<Tag, false><<<grid, kBlock, 0, st>>>(a);
+  }
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+extern "C" int sp_embedding_pool(void* out, int64_t out_stride, const void* x, int64_t x_stride,
+                                 const void* residual, int64_t res_stride, const void* weight, float eps,
+                                 const void* extend_seq_lens, int idx64, int num_seqs, int64_t num_tokens,
+                                 int hidden, int normalize, int dtype, void* stream) {
+  SP_CHECK_ARG(num_seqs >= 0 && num_tokens >= 0 && hidden > 0);
+  SP_CHECK_ARG(out && x && extend_seq_lens);
+  SP_CHECK_ARG(out_stride >= hidden && x_stride >= hidden);
+  if (residual) SP_CHECK_ARG(weight && res_stride >= hidden);
+  if (weight) SP_CHECK_ARG(eps > 0.f);
+  if (dtype != SP_F32 && dtype != SP_F16 && dtype != SP_BF16) return SP_ERR_UNSUPPORTED;
+  if (num_seqs == 0) return SP_OK;
+  EmbedArgs a;
+  a.out = out; a.x = x; a.residual = residual; a.weight = weight; a.lens = extend_seq_lens;
+  a.o_stride = out_stride; a.x_stride = x_stride; a.r_stride = residual ? res_stride : 0;
+  a.num_tokens = num_tokens; a.hidden = hidden; a.idx64 = idx64 ? 1 : 0; a.normalize = normalize ? 1 : 0;
+  a.out_vec = 0; a.eps = eps;
+  SP_DISPATCH_DTYPE(dtype, return (launch_embedding_pool<Tag>(a, num_seqs, (hipStream_t)stream)));
 }
 
 template <typename Tag>

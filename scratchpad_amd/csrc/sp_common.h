@@ -219,6 +219,7 @@ __device__ __forceinline__ u32x4 bf16x8_to_f16x8(const u32x4& v) {
 }
 
 // ---- wave reductions ------------------------------------------------------------------------
+// (the depth of this butterfly enters the error bound of the embedding-pool tests, with block_sum's: DESIGN.md 4.2b)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -1,9 +1,11 @@
-"""RMSNorm / SiluAndMul / XIELU / rotary embedding modules over the HIP kernels.
+"""RMSNorm / SiluAndMul / XIELU / rotary embedding / Pooler modules over the HIP kernels.
 
-Mirrors nn/layers/layernorm.py:12-32, nn/layers/activation.py:21-60 and
-nn/layers/rotary_embedding.py:52-170, 677-720, 918-1088 (same class names, constructor
+Mirrors nn/layers/layernorm.py:12-32, nn/layers/activation.py:21-60,
+nn/layers/rotary_embedding.py:52-170, 677-720, 918-1088 and nn/layers/pooler.py (same class names, constructor
 arguments, return conventions and in-place contracts)."""
 import math
+from dataclasses import dataclass
+from enum import IntEnum
 from typing import Any, Dict, Optional, Tuple, Union
 
 import torch
@@ -54,6 +56,49 @@ class XIELU(CustomOp):
 
     def forward_hip(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         return _native.xielu(x, self.alpha_p.data, self.alpha_n.data, self.beta, self.eps, out=out)
+
+
+class PoolingType(IntEnum):
+    """pooler.py:13-14"""
+    LAST = 0
+
+
+@dataclass
+class EmbeddingPoolerOutput:
+    """pooler.py:17-19"""
+    embeddings: torch.Tensor
+
+
+class Pooler(nn.Module):
+    """pooler.py:22-50: the hidden state of every sequence's last token, L2-normalised when ``normalize`` is set -
+    cumsum, gather and F.normalize as ONE launch (sp_embedding_pool).  ``forward`` is the reference's call on normed
+    hidden states; ``forward_prenorm`` is handed the decoder's output BEFORE its final norm and applies that norm to
+    the pooled rows alone, inside the same launch (the bits are those of the norm over all rows followed by
+    ``forward``).  Neither writes its inputs.  No parameters."""
+
+    def __init__(self, pooling_type: PoolingType, normalize: bool):
+        super().__init__()
+        self.pooling_type = pooling_type
+        self.normalize = normalize
+
+    def _check(self, forward_batch) -> None:
+        if self.pooling_type != PoolingType.LAST:
+            raise ValueError(f"Invalid pooling type: {self.pooling_type}")
+        if forward_batch.extend_seq_lens is None:
+            raise ValueError("Pooler needs an extend batch (ForwardBatch.extend_seq_lens)")
+
+    def forward(self, hidden_states: torch.Tensor, forward_batch) -> EmbeddingPoolerOutput:
+        self._check(forward_batch)
+        return EmbeddingPoolerOutput(embeddings=_native.embedding_pool(
+            hidden_states, forward_batch.extend_seq_lens, self.normalize))
+
+    def forward_prenorm(self, hidden_states: torch.Tensor, residual: Optional[torch.Tensor], final_norm: "RMSNorm",
+                        forward_batch) -> EmbeddingPoolerOutput:
+        """Pooler(final_norm(hidden_states, residual)[0]) without norming the rows nobody reads"""
+        self._check(forward_batch)
+        return EmbeddingPoolerOutput(embeddings=_native.embedding_pool(
+            hidden_states, forward_batch.extend_seq_lens, self.normalize, residual=residual,
+            weight=final_norm.weight.data, eps=final_norm.variance_epsilon))
 
 
 class RotaryEmbedding(CustomOp):

@@ -23,7 +23,7 @@ from .distributed import (divide, get_tensor_model_parallel_rank,
                           get_tensor_model_parallel_world_size, get_tp_group, tensor_model_parallel_all_gather,
                           tensor_model_parallel_all_reduce)
 from .forward_info import ForwardBatch
-from .layers import RMSNorm, SiluAndMul, get_rope
+from .layers import EmbeddingPoolerOutput, Pooler, PoolingType, RMSNorm, SiluAndMul, get_rope
 
 
 class LogitsProcessorOutput:
@@ -557,18 +557,41 @@ class LlamaModel(nn.Module):
         self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
     def forward(self, input_ids, positions, forward_batch: ForwardBatch,
-                input_embeds: torch.Tensor = None) -> torch.Tensor:
+                input_embeds: torch.Tensor = None, before_final_norm: bool = False) -> torch.Tensor:
+        """before_final_norm (TP = 1 only): return (hidden_states, residual) as the last layer leaves them, for a
+        caller that norms only the rows it reads (Pooler.forward_prenorm)."""
         hidden_states = self.embed_tokens(input_ids) if input_embeds is None else input_embeds
         residual = None
         # under TP every row-parallel all-reduce is handed to the norm behind it (2 x layers per step)
         defer = get_tensor_model_parallel_world_size() > 1
         for layer in self.layers:
             hidden_states, residual = layer(positions, hidden_states, forward_batch, residual, defer)
+        if before_final_norm:
+            if defer:
+                raise ValueError("before_final_norm under tensor parallelism: the hidden states are partial sums")
+            return hidden_states, residual
         if defer:
             hidden_states, _ = norm_after_row_parallel(self.norm, hidden_states, residual)
         else:
             hidden_states, _ = self.norm(hidden_states, residual)
         return hidden_states
+
+
+def pooled_embedding(decoder: nn.Module, pooler: Pooler, input_ids, positions, forward_batch: ForwardBatch,
+                     input_embeds: torch.Tensor = None) -> EmbeddingPoolerOutput:
+    """The ``get_embedding`` branch of the reference's models (llama.py:300-303, qwen3.py:247-250,
+    llama_embedding.py:36-37): the decoder, then the pooler.  At TP = 1 the decoder stops before its final norm and
+    one sp_embedding_pool launch norms, gathers and normalises the B rows that are read; under TP the final norm is
+    the all-reduce's (norm_after_row_parallel over all rows) and the launch gathers and normalises."""
+    if forward_batch is None or not forward_batch.forward_mode.is_extend():
+        raise ValueError("get_embedding=True needs an extend (prefill) batch: a decode batch has no sequence to pool")
+    if forward_batch.return_logprob:
+        raise NotImplementedError("return_logprob on an embedding batch: an embedding pass computes no logits")
+    if get_tensor_model_parallel_world_size() > 1:
+        hidden_states = decoder(input_ids, positions, forward_batch, input_embeds)
+        return pooler(hidden_states, forward_batch)
+    hidden_states, residual = decoder(input_ids, positions, forward_batch, input_embeds, before_final_norm=True)
+    return pooler.forward_prenorm(hidden_states, residual, decoder.norm, forward_batch)
 
 
 class LlamaForCausalLM(nn.Module):
@@ -581,10 +604,13 @@ class LlamaForCausalLM(nn.Module):
         else:
             self.lm_head = ParallelLMHead(config.vocab_size, config.hidden_size, dtype)
         self.logits_processor = LogitsProcessor(config)
+        self.pooler = Pooler(pooling_type=PoolingType.LAST, normalize=True)
 
     @torch.no_grad()
     def forward(self, input_ids, positions, forward_batch: ForwardBatch,
-                input_embeds: torch.Tensor = None) -> LogitsProcessorOutput:
+                input_embeds: torch.Tensor = None, get_embedding: bool = False) -> LogitsProcessorOutput:
+        if get_embedding:
+            return pooled_embedding(self.model, self.pooler, input_ids, positions, forward_batch, input_embeds)
         hidden_states = self.model(input_ids, positions, forward_batch, input_embeds)
         return self.logits_processor(input_ids, hidden_states, self.lm_head, forward_batch)
 

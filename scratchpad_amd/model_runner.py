@@ -3,10 +3,11 @@
 Mirrors the hot-path parts of model_executor/model_runner.py (init_memory_pool 360-442,
 init_attention_backend 453-470, forward/forward_decode/forward_extend 506-537, sample 539-563),
 model_executor/cuda_graph_runner.py:144-521 (static-buffer capture / padded replay) and
-managers/tp_worker.py:164-169 (forward_batch_generation).  LoRA toppings: scratchpad_amd/toppings.py.  Weight
+managers/tp_worker.py:164-175 (forward_batch_generation, forward_batch_embedding).  LoRA toppings: scratchpad_amd/toppings.py.  Weight
 loading, offload, speculative decoding and the NVML/zmq control plane are out of scope.
 """
 import bisect
+import dataclasses
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
@@ -43,18 +44,28 @@ class ModelConfig:
     pad_token_id: Optional[int] = None
     # Mllama: the vision tower's config (MllamaVisionConfig fields); None = text side only
     vision_config: Optional[object] = None
-    # which decoder load_model builds: "llama" (with cross_attention_layers: Mllama), "qwen3", "apertus" or
-    # "llama_moe"
+    # which decoder load_model builds: "llama" (with cross_attention_layers: Mllama), "qwen3", "apertus",
+    # "llama_moe" or "llama_embedding" (scratchpad_amd/llama_embedding.py: the Llama decoder without an LM head)
     architecture: str = "llama"
     attention_bias: bool = False        # Qwen3: refused when set (scratchpad_amd/qwen3.py)
     # Llama-MoE (scratchpad_amd/llama_moe.py): experts per layer and experts a token is routed to
     num_experts: Optional[int] = None
     experts_per_token: Optional[int] = None
     grouped_topk: bool = False          # refused when set: plain top-k routing only
+    # serve a generative architecture's checkpoint for embedding requests (server args' is_embedding)
+    is_embedding: bool = False
 
     @property
     def is_encoder_decoder(self) -> bool:
         return bool(self.cross_attention_layers)
+
+    @property
+    def is_generation(self) -> bool:
+        """config/model_config.py:13-26: an embedding architecture never generates; any other does unless it is
+        served with is_embedding"""
+        if self.architecture == "llama_embedding":
+            return False
+        return not self.is_embedding
 
     def __post_init__(self):
         if self.head_dim is None:
@@ -62,8 +73,13 @@ class ModelConfig:
         if self.architecture in ("llama_quant_moe", "llama_naive_quant_moe"):
             raise NotImplementedError(f"architecture {self.architecture!r}: the quantised MoE models are out of scope "
                                       "(llama_moe is the one that is built)")
-        if self.architecture not in ("llama", "qwen3", "apertus", "llama_moe"):
-            raise ValueError(f"Unsupported architecture: {self.architecture!r} (llama, qwen3, apertus, llama_moe)")
+        if self.architecture not in ("llama", "qwen3", "apertus", "llama_moe", "llama_embedding"):
+            raise ValueError(f"Unsupported architecture: {self.architecture!r} (llama, qwen3, apertus, llama_moe, "
+                             "llama_embedding)")
+        if not self.is_generation and (self.architecture in ("apertus", "llama_moe") or self.cross_attention_layers):
+            raise NotImplementedError(f"embedding requests on {self.architecture!r}"
+                                      f"{' with cross-attention layers' if self.cross_attention_layers else ''}: the "
+                                      "pooler branch is built for llama, qwen3 and llama_embedding")
         if self.architecture == "llama_moe":
             if self.grouped_topk:
                 raise NotImplementedError("grouped_topk is not built: plain top-k routing only")
@@ -138,6 +154,14 @@ class ModelConfig:
                    max_position_embeddings=max(32768, context_len), architecture="llama_moe", num_experts=8,
                    experts_per_token=2)
 
+    @classmethod
+    def e5_mistral_7b(cls, context_len: int = 4096):
+        """e5-mistral-7b-instruct: Mistral-7B widths under the Llama decoder, served for embeddings.  The figures are
+        written from memory of the released configuration and are UNVERIFIED against it; the
+        checkpoint's sliding window is not modelled (context_len stays inside it)."""
+        return cls(4096, 14336, 32, 32, 8, 32000, context_len=context_len, rms_norm_eps=1e-5, rope_theta=10000.0,
+                   max_position_embeddings=max(32768, context_len), architecture="llama_embedding")
+
 
 @dataclass
 class ServerArgs:
@@ -156,6 +180,8 @@ class ServerArgs:
     # args.py max_prefill_tokens: the most tokens one extend batch carries (the scheduler's limit, TpModelWorker); the
     # per-token topping index buffer is sized by it
     max_prefill_tokens: int = 16384
+    # args.py is_embedding: serve the model for embedding requests (ModelConfig.is_embedding is set from it)
+    is_embedding: bool = False
 
 
 def get_batch_sizes_to_capture(server_args: ServerArgs, max_reqs: int) -> List[int]:
@@ -177,6 +203,9 @@ class ModelRunner:
         One without the other is refused.  An extend batch may carry ``server_args.max_prefill_tokens`` tokens."""
         self.model_config = model_config
         self.server_args = server_args or ServerArgs()
+        if self.server_args.is_embedding and not model_config.is_embedding:
+            model_config = self.model_config = dataclasses.replace(model_config, is_embedding=True)
+        self.is_generation = model_config.is_generation
         if bool(toppings) != bool(self.server_args.max_toppings_per_batch):
             raise ValueError("toppings and ServerArgs.max_toppings_per_batch go together: adapters without slots (or "
                              "slots without adapters) would serve the base model to requests that name an adapter")
@@ -230,6 +259,9 @@ class ModelRunner:
                     raise NotImplementedError("Llama-MoE under tensor parallelism (TP > 1) is out of scope")
                 from .llama_moe import LlamaMoEForCausalLM
                 self.model = LlamaMoEForCausalLM(self.model_config, dtype=self.dtype).eval()
+            elif self.model_config.architecture == "llama_embedding":
+                from .llama_embedding import LlamaEmbeddingModel
+                self.model = LlamaEmbeddingModel(self.model_config, dtype=self.dtype).eval()
             else:
                 self.model = LlamaForCausalLM(self.model_config, dtype=self.dtype).eval()
         for p in self.model.parameters():
@@ -295,6 +327,8 @@ class ModelRunner:
 
     def init_cuda_graphs(self):
         """model_runner.py:490-504."""
+        if not self.is_generation:
+            return      # model_runner.py:496-498: an embedding model has no decode step to capture
         if self.server_args.disable_cuda_graph:
             return
         if _native._LIBROWS_MODE == "auto":
@@ -324,11 +358,21 @@ class ModelRunner:
         return self.model.forward(forward_batch.input_ids, forward_batch.positions, forward_batch)
 
     def forward_decode(self, forward_batch: ForwardBatch) -> LogitsProcessorOutput:
+        if not self.is_generation:
+            raise ValueError("forward_decode on a non-generative (embedding) runner: embedding requests are "
+                             "prefill only")
         self.attn_backend.init_forward_metadata(forward_batch)
         return self._run_model(forward_batch)
 
-    def forward_extend(self, forward_batch: ForwardBatch) -> LogitsProcessorOutput:
+    def forward_extend(self, forward_batch: ForwardBatch):
+        """model_runner.py:516-529: a generative runner returns logits, a non-generative one the pooler's
+        EmbeddingPoolerOutput (``get_embedding=True``)"""
+        if not self.is_generation and forward_batch.return_logprob:
+            raise NotImplementedError("return_logprob on an embedding batch: an embedding pass computes no logits")
         self.attn_backend.init_forward_metadata(forward_batch)
+        if not self.is_generation:
+            return self.model.forward(forward_batch.input_ids, forward_batch.positions, forward_batch,
+                                      get_embedding=True)
         return self._run_model(forward_batch)
 
     def forward(self, forward_batch: ForwardBatch) -> LogitsProcessorOutput:
@@ -354,6 +398,8 @@ class ModelRunner:
         in the synchronous and the overlap worker (the reference cumulates in prepare_for_decode and has to rebuild
         a host list of the delayed tokens under overlap, schedule_batch.py:1254-1275).  A batch without penalties or
         grammars takes none of these steps."""
+        if not self.is_generation:
+            raise ValueError("sample on a non-generative (embedding) runner: there are no logits to sample from")
         info = forward_batch.sampling_info
         if forward_batch.penalty_seed:
             # requests this batch admits: forget what the previous owner of their pool rows left and replay their own
@@ -564,3 +610,12 @@ class TpModelWorker:
         if skip_sample:
             return logits_output, None
         return logits_output, self.model_runner.sample(logits_output, forward_batch)
+
+    def forward_batch_embedding(self, model_worker_batch: ModelWorkerBatch) -> torch.Tensor:
+        """tp_worker.py:171-175: [B, hidden] embeddings in the model dtype, one row per request of the batch"""
+        if self.model_runner.is_generation:
+            raise ValueError("forward_batch_embedding on a generative runner: build it with ServerArgs.is_embedding "
+                             "or an embedding architecture")
+        forward_batch = ForwardBatch.init_new(model_worker_batch, self.model_runner)
+        logits_output = self.model_runner.forward(forward_batch)
+        return logits_output.embeddings

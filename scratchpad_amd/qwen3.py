@@ -9,8 +9,8 @@ all-reduce protocol under tensor parallelism, weight loading - is llama.py's and
 
 On the fused path (``HipAttnBackend.fused_rope_kv_store``) the two norms, the rotation and the KV store are ONE launch
 (sp_qk_norm_rotary), bit-identical to the reference's order norm, norm, rotary, store, which the non-fused branch runs.
-The q_norm / k_norm weights are [head_dim] and replicated on every tensor-parallel rank.  The reference's
-``get_embedding`` / pooler branch is not built."""
+The q_norm / k_norm weights are [head_dim] and replicated on every tensor-parallel rank.  ``forward(get_embedding=True)``
+is the reference's pooler branch (qwen3.py:247-250): llama.pooled_embedding."""
 from typing import Any, Dict, Optional, Tuple
 
 import torch
@@ -19,9 +19,10 @@ from torch import nn
 from .attention import RadixAttention
 from .distributed import get_tensor_model_parallel_world_size
 from .forward_info import ForwardBatch
-from .layers import RMSNorm, get_rope
+from .layers import Pooler, PoolingType, RMSNorm, get_rope
 from .llama import (LlamaForCausalLM, LlamaMLP, LogitsProcessor, LogitsProcessorOutput, ParallelLMHead,
-                    QKVParallelLinear, RowParallelLinear, VocabParallelEmbedding, norm_after_row_parallel)
+                    QKVParallelLinear, RowParallelLinear, VocabParallelEmbedding, norm_after_row_parallel,
+                    pooled_embedding)
 
 
 class Qwen3Attention(nn.Module):
@@ -132,12 +133,17 @@ class Qwen3Model(nn.Module):
         self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
     def forward(self, input_ids, positions, forward_batch: ForwardBatch,
-                input_embeds: torch.Tensor = None) -> torch.Tensor:
+                input_embeds: torch.Tensor = None, before_final_norm: bool = False) -> torch.Tensor:
+        """before_final_norm: as LlamaModel.forward"""
         hidden_states = self.embed_tokens(input_ids) if input_embeds is None else input_embeds
         residual = None
         defer = get_tensor_model_parallel_world_size() > 1
         for layer in self.layers:
             hidden_states, residual = layer(positions, hidden_states, forward_batch, residual, defer)
+        if before_final_norm:
+            if defer:
+                raise ValueError("before_final_norm under tensor parallelism: the hidden states are partial sums")
+            return hidden_states, residual
         if defer:
             hidden_states, _ = norm_after_row_parallel(self.norm, hidden_states, residual)
         else:
@@ -155,10 +161,13 @@ class Qwen3ForCausalLM(nn.Module):
         else:
             self.lm_head = ParallelLMHead(config.vocab_size, config.hidden_size, dtype)
         self.logits_processor = LogitsProcessor(config)
+        self.pooler = Pooler(pooling_type=PoolingType.LAST, normalize=True)
 
     @torch.no_grad()
     def forward(self, input_ids, positions, forward_batch: ForwardBatch,
-                input_embeds: torch.Tensor = None) -> LogitsProcessorOutput:
+                input_embeds: torch.Tensor = None, get_embedding: bool = False) -> LogitsProcessorOutput:
+        if get_embedding:
+            return pooled_embedding(self.model, self.pooler, input_ids, positions, forward_batch, input_embeds)
         hidden_states = self.model(input_ids, positions, forward_batch, input_embeds)
         return self.logits_processor(input_ids, hidden_states, self.lm_head, forward_batch)
 
