@@ -500,6 +500,49 @@ SP_API int sp_lora_expand(void* y, const float* tmp, const void* b, const int32_
                    int r, int n, int num_slices, int num_slots, int64_t y_stride, int64_t tmp_stride,
                    int64_t b_slot_stride, int dtype, void* stream);
 
+/* ---- Delta toppings (additive in ABI 10): the DeltaW= half of the topping layers' ldmm(...) calls
+ *      (nn/toppings/topping_layer.py) - a full-model delta W_finetuned - W_base per adapter slot, stored 4-bit and 2:4
+ *      sparse (3 bits per dense weight), multiplied per row and added to the base projection's output.
+ * The packed format (THIS library's; the reference's buffers are in triteia's Marlin tile order, which is not
+ *      converted).  One projection, dense delta D[N, K] (output rows x input width, as the weights), per slot:
+ *        codes  uint8 [N, K / 4]: byte g of row n is the group of columns 4 g .. 4 g + 3, of which two positions
+ *               p0 < p1 are kept; low nibble = the code at p0, high nibble = the code at p1, codes in 0..15;
+ *        meta   uint8 [N, K / 8]: byte m holds group 2 m in its low and group 2 m + 1 in its high nibble; a nibble is
+ *               p0 | p1 << 2 and MUST have p0 < p1;
+ *        scales [N] in `dtype`: D[n, 4 g + p] = scales[n] * (code - 8) at the two kept positions, 0 elsewhere.
+ *      Stacked projections are stacked by rows (q | k | v, gate | up).  Slot strides: bytes for codes and meta,
+ *      elements for scales.  A slot filled with code 8 (any valid meta, any finite scale) adds exactly 0: its rows of y
+ *      are still rewritten, y + (+0.0), so a -0.0 there becomes +0.0 and every other value keeps its bits.
+ * sp_delta_group: the stable counting sort of the rows t with 0 <= indices[t] < num_slots, by slot: slot_offsets int32
+ *      [num_slots + 1], sorted_rows int32 [num_tokens] of which only the first slot_offsets[num_slots] entries are
+ *      defined, ascending within a slot.  A row with any other index (the -1 of a base-model request, a padded graph
+ *      row) appears nowhere.  No atomics: the order is a function of the indices alone.  One launch, also for
+ *      num_tokens == 0 (slot_offsets then reads all zero).
+ * sp_delta_mm: for every sorted row t of slot s, in place,
+ *        y[t, n] = round_dtype( y[t, n] + scales_s[n] * sum_k x[t, k] * q_s[n, k] )        q = code - 8, an integer
+ *      with ONE fp32 accumulation (the operands q are exact in fp16 / bf16), the scale applied once in fp32 behind the
+ *      sum, one rounding.  The sum runs over super-steps of 256 columns dealt round-robin to 8 partial sums, each a
+ *      chain of v_mfma_f32_16x16x32 (8 per super-step), folded in order: depth c(K) = 33 * 8 * ceil(ceil(K / 256) / 8)
+ *      + 10 fp32 roundings at most.  A row that is in no group is neither read nor written and no address is formed
+ *      from its index; every sorted row is checked against [0, num_tokens) first.  Every (t, n) has one writer provided
+ *      sorted_rows names a row once (sp_delta_group does).  A slot without rows costs no weight traffic.
+ * Batch invariance: the bits a row receives depend on that row's x and y, its slot's packed delta and (N, K) only - not
+ *      on num_tokens, the row's position, its neighbours or how many rows its slot has.
+ * SP_ERR_UNSUPPORTED: num_slots == 0 or > 64; num_tokens > 16384; (sp_delta_mm) a dtype other than fp16 / bf16, K not
+ *      a positive multiple of 64, N not a positive multiple of 16 or above 1048560.
+ * SP_ERR_INVALID_ARG before any launch: a NULL pointer, a negative size, x_stride < K, y_stride < N,
+ *      codes_slot_stride < N K / 4, meta_slot_stride < N K / 8, scales_slot_stride < N; x or codes not 16-byte aligned,
+ *      meta not 8-byte aligned, y or scales not 2-byte aligned, x_stride not a multiple of 8, codes_slot_stride not a
+ *      multiple of 16, meta_slot_stride not a multiple of 8.  sp_delta_mm with num_tokens == 0 is SP_OK without a
+ *      launch.  Like sp_gemm_skinny these entries sit on the decode step and do not ask the runtime whether their
+ *      pointers are device memory.                                                                                 */
+SP_API int sp_delta_group(int32_t* slot_offsets, int32_t* sorted_rows, const int32_t* indices, int64_t num_tokens,
+                   int num_slots, void* stream);
+SP_API int sp_delta_mm(void* y, const void* x, const void* codes, const void* meta, const void* scales,
+                const int32_t* slot_offsets, const int32_t* sorted_rows, int64_t num_tokens, int num_slots, int N,
+                int K, int64_t x_stride, int64_t y_stride, int64_t codes_slot_stride, int64_t meta_slot_stride,
+                int64_t scales_slot_stride, int dtype, void* stream);
+
 /* ---- Mixture of experts (additive in ABI 10): LlamaMoE.forward (nn/models/llama/llama_moe.py:98-120) as launches
  *      whose grids depend on (num_tokens, top_k, num_experts) and the widths alone; the grouping is read from device
  *      memory, so a captured sequence follows the routing of every replay.  T = num_tokens, K = top_k, E = num_experts.

@@ -114,6 +114,9 @@ SIGNATURES = {
     "sp_gemm_skinny_xielu": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _i32, _vp]),
     "sp_lora_shrink": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _f32, _i32, _vp]),
     "sp_lora_expand": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
+    "sp_delta_group": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "sp_delta_mm": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i32,
+                           _vp]),
     "sp_moe_block_rows": (_i32, []),
     "sp_moe_max_tokens": (_i32, []),
     "sp_moe_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _vp]),
@@ -1334,6 +1337,63 @@ def lora_expand(y: torch.Tensor, tmp: torch.Tensor, B: torch.Tensor, indices: to
                                  B.shape[0], y.stride(0), tmp.stride(0), B.stride(0), _dt(y), _stream()),
            "sp_lora_expand")
     LORA_CALLS["expand"] += 1
+    return y
+
+
+# --------------------------------------------------------------------------- delta toppings
+# launches by entry ("group" = sp_delta_group, "mm" = sp_delta_mm): tests prove with it that a step ran the kernels
+DELTA_CALLS = {"group": 0, "mm": 0}
+DELTA_MAX_SLOTS = 64
+DELTA_MAX_TOKENS = 16384
+
+
+def delta_group(indices: torch.Tensor, num_tokens: int, num_slots: int, slot_offsets: torch.Tensor,
+                sorted_rows: torch.Tensor) -> None:
+    """sp_delta_group over the first ``num_tokens`` entries of ``indices`` (contiguous int32), into the caller's
+    persistent int32 buffers ``slot_offsets`` [>= num_slots + 1] and ``sorted_rows`` [>= num_tokens]."""
+    _gpu(indices, slot_offsets, sorted_rows)
+    T, S = int(num_tokens), int(num_slots)
+    _lora_indices(indices, T, "delta_group")
+    for t, n, what in ((slot_offsets, S + 1, "slot_offsets"), (sorted_rows, T, "sorted_rows")):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < n or (t.shape[0] > 1 and t.stride(0) != 1):
+            raise RuntimeError(f"delta_group: {what} must be a contiguous int32 vector of at least {n} entries")
+    _check(load().sp_delta_group(slot_offsets.data_ptr(), sorted_rows.data_ptr(), indices.data_ptr(), T, S, _stream()),
+           "sp_delta_group")
+    DELTA_CALLS["group"] += 1
+
+
+def delta_mm(y: torch.Tensor, x: torch.Tensor, codes: torch.Tensor, meta: torch.Tensor, scales: torch.Tensor,
+             slot_offsets: torch.Tensor, sorted_rows: torch.Tensor) -> torch.Tensor:
+    """y[t] += scales[s] * (x[t] @ q[s]^T) in place for every sorted row t of slot s (sp_delta_mm): y [T, >= N] (a
+    column view of a wider activation is fine), x [T, K] row-contiguous, codes uint8 [slots, N, K / 4], meta uint8
+    [slots, N, K / 8], scales [slots, N] in y's dtype (the layer views of ToppingMemPool's delta buffers), the grouping
+    as delta_group left it.  Rows in no group are left alone."""
+    _gpu(y, x, codes, meta, scales, slot_offsets, sorted_rows)
+    if y.dim() != 2 or x.dim() != 2 or y.stride(1) != 1 or x.stride(1) != 1 or x.dtype != y.dtype \
+            or x.shape[0] != y.shape[0]:
+        raise RuntimeError(f"delta_mm: y [T, >= N] and x [T, K] with contiguous rows, of one dtype; got y "
+                           f"{tuple(y.shape)} {y.dtype}, x {tuple(x.shape)} {x.dtype}")
+    T, K = x.shape
+    if codes.dim() != 3 or meta.dim() != 3 or scales.dim() != 2 or codes.dtype != torch.uint8 \
+            or meta.dtype != torch.uint8 or scales.dtype != y.dtype:
+        raise RuntimeError("delta_mm: codes / meta uint8 [slots, N, .] and scales [slots, N] in y's dtype")
+    S, N = codes.shape[0], codes.shape[1]
+    if K % 8 != 0 or tuple(codes.shape) != (S, N, K // 4) or tuple(meta.shape) != (S, N, K // 8) \
+            or tuple(scales.shape) != (S, N) or y.shape[1] < N \
+            or codes.stride(2) != 1 or codes.stride(1) != K // 4 or meta.stride(2) != 1 or meta.stride(1) != K // 8 \
+            or scales.stride(1) != 1:
+        raise RuntimeError(f"delta_mm: codes {tuple(codes.shape)}, meta {tuple(meta.shape)}, scales "
+                           f"{tuple(scales.shape)} do not describe [slots, N, K = {K}] slots with contiguous rows for "
+                           f"y {tuple(y.shape)}")
+    for t, n, what in ((slot_offsets, S + 1, "slot_offsets"), (sorted_rows, T, "sorted_rows")):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < n or (t.shape[0] > 1 and t.stride(0) != 1):
+            raise RuntimeError(f"delta_mm: {what} must be a contiguous int32 vector of at least {n} entries")
+    if T == 0:
+        return y
+    _check(load().sp_delta_mm(y.data_ptr(), x.data_ptr(), codes.data_ptr(), meta.data_ptr(), scales.data_ptr(),
+                              slot_offsets.data_ptr(), sorted_rows.data_ptr(), T, S, N, K, x.stride(0), y.stride(0),
+                              codes.stride(0), meta.stride(0), scales.stride(0), _dt(y), _stream()), "sp_delta_mm")
+    DELTA_CALLS["mm"] += 1
     return y
 
 

@@ -1,0 +1,309 @@
+// Delta toppings: the per-row product with a 4-bit, 2:4-sparse full-model delta (W_finetuned - W_base) of the row's
+// adapter slot, added in place to the base projection's output.
+//
+// Call sites they serve: the DeltaW= half of every ldmm(...) call of the topping layers
+// (nn/toppings/topping_layer.py) over the buffers of memory/topping_pool.py:126-172.  The reference hands the arithmetic
+// to triteia (not part of its tree) over Marlin-ordered buffers; the layout here is this project's own
+// (include/scratchpad_hip.h states it): per slot and output row n, byte g of `codes` is the group of dense columns
+// 4 g .. 4 g + 3 (low nibble: the code at p0, high nibble: the code at p1 > p0), nibble g of `meta` is p0 | p1 << 2,
+// and the dense value is scales[n] * (code - 8).  The lanes of a row read contiguous bytes.
+//
+//   sp_delta_group  the stable counting sort of the rows t with 0 <= indices[t] < slots by slot: slot_offsets[slots + 1],
+//                   sorted_rows[T].  ONE workgroup, moe_sort_kernel's method (csrc/moe.hip): thread i counts the slots
+//                   of the i-th contiguous chunk of rows into its own LDS column, a flat prefix over [slot][thread]
+//                   gives every (slot, thread) its first entry, the thread writes its chunk in order.  No atomic.
+//   sp_delta_mm     y[t, n] = round(y[t, n] + scale_s[n] * sum_k x[t, k] * q_s[n, k])  for every sorted row t of slot s
+//
+// The product is moe_gemm_kernel (csrc/moe.hip) with "expert" = slot, top-k = 1 and the weight operand unpacked in
+// registers:
+//   * a workgroup (8 waves) owns kDeltaBM = 32 consecutive sorted rows of ONE slot x 16 rows of that slot's delta;
+//   * grid.x = ceil(T / BM) + slots row blocks, an upper bound computed from (T, slots); wave 0 finds the block's
+//     (slot, first row) from slot_offsets with one wave prefix sum and the workgroup exits if there is none, so a slot
+//     without rows costs no weight traffic;
+//   * the reduction is cut into super-steps of 256 dense columns, which the 8 waves take round-robin.  In a super-step
+//     lane (r16, q) loads 16 B of codes and 8 B of meta of delta row n0 + r16 - the 64 dense columns 256 ss + 64 q ..
+//     + 63 - and spends them over 8 v_mfma_f32_16x16x32: k-slot (q, i) of MFMA j carries dense column
+//     256 ss + 64 q + 8 j + i, so the activation operand of MFMA j is the 16 B at that column of the lane's row (two
+//     16-row sub-blocks: one unpacked fragment feeds 2 MFMAs).  A tail super-step (K % 256 != 0) has lanes whose 64
+//     columns lie past K: they load nothing and feed zeros on both sides.  No LDS on the way in;
+//   * unpacking is VALU: a code byte becomes two 16-bit floats through the exponent trick (0x6400 | c is 1024 + c in
+//     fp16, 0x4300 | c is 128 + c in bf16; subtracting 1032 resp. 136 leaves the integer c - 8 exactly), and the pair is
+//     shifted to the 16-bit positions p0 and p1 of the group's four;
+//   * the waves' partial tiles are summed through LDS in wave order, multiplied by the row's scale, added to y and
+//     rounded once.  Every (t, n) has one writer.
+// The sparse MFMA (v_smfmac_f32_16x16x64) is not used: see DESIGN.md 4.6c.
+//
+// BATCH INVARIANCE: the bits a row receives depend on that row's x and y, its slot's packed delta and (N, K) only.  The
+// super-steps of a wave, the 8 MFMAs inside one and the order over the waves are functions of K alone; a row's position
+// inside its block only selects the lane column of the MFMA, and rows that are absent feed zeros into columns of their
+// own.
+//
+// Safety: every sorted row is checked against [0, T) before an address is formed from it; rows past a slot's end and
+// rows in no group are never loaded or stored; the offsets read from slot_offsets are clamped to [0, T]; all byte
+// offsets are 64-bit.
+#include "sp_common.h"
+
+namespace sp {
+
+constexpr int kDeltaMaxSlots = 64;
+constexpr int kDeltaMaxTokens = 16384;
+constexpr int kDeltaWaves = 8;
+constexpr int kDeltaMB = 2;                // 16-row sub-blocks of a workgroup
+constexpr int kDeltaBM = 16 * kDeltaMB;
+constexpr int kDeltaSortThreads = 128;
+
+// ------------------------------------------------------------------------------------------------ group
+__global__ __launch_bounds__(kDeltaSortThreads) void delta_group_kernel(int32_t* offsets, int32_t* sorted_rows,
+                                                                        const int32_t* indices, int T, int S) {
+  __shared__ int hist[kDeltaMaxSlots * kDeltaSortThreads];   // [slot][thread]
+  __shared__ int part[kDeltaSortThreads];
+  const int tid = threadIdx.x;
+  const int chunk = (T + kDeltaSortThreads - 1) / kDeltaSortThreads;
+  const int c0 = min(tid * chunk, T), c1 = min(c0 + chunk, T);
+  for (int s = 0; s < S; ++s) hist[s * kDeltaSortThreads + tid] = 0;
+  for (int t = c0; t < c1; ++t) {
+    const int id = indices[t];
+    if ((unsigned)id < (unsigned)S) ++hist[id * kDeltaSortThreads + tid];
+  }
+  __syncthreads();
+  // exclusive prefix over the flat [slot][thread] order: thread tid owns entries tid S .. tid S + S - 1
+  int sum = 0;
+  for (int j = 0; j < S; ++j) sum += hist[tid * S + j];
+  part[tid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int i = 0; i < kDeltaSortThreads; ++i) {
+      const int x = part[i];
+      part[i] = run;
+      run += x;
+    }
+  }
+  __syncthreads();
+  int run = part[tid];
+  for (int j = 0; j < S; ++j) {
+    const int x = hist[tid * S + j];
+    hist[tid * S + j] = run;
+    run += x;
+  }
+  if (tid == kDeltaSortThreads - 1) offsets[S] = run;       // rows with an index in [0, S)
+  __syncthreads();
+  if (tid < S) offsets[tid] = hist[tid * kDeltaSortThreads];
+  __syncthreads();
+  for (int t = c0; t < c1; ++t) {
+    const int id = indices[t];
+    if ((unsigned)id < (unsigned)S) sorted_rows[hist[id * kDeltaSortThreads + tid]++] = t;   // < offsets[S] <= T
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ product
+typedef float f32x4_d __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_d __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_d __attribute__((ext_vector_type(8)));
+
+template <typename Tag>
+__device__ __forceinline__ f32x4_d mfma_d(const u32x4& a, const u32x4& b, const f32x4_d& c);
+template <>
+__device__ __forceinline__ f32x4_d mfma_d<bf16_tag>(const u32x4& a, const u32x4& b, const f32x4_d& c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_d, a), __builtin_bit_cast(bf16x8_d, b),
+                                                 c, 0, 0, 0);
+}
+template <>
+__device__ __forceinline__ f32x4_d mfma_d<f16_tag>(const u32x4& a, const u32x4& b, const f32x4_d& c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_d, a), __builtin_bit_cast(f16x8_d, b),
+                                                c, 0, 0, 0);
+}
+
+// one code byte -> (code_lo - 8) in the low and (code_hi - 8) in the high 16 bits, in the activation dtype, exactly
+template <typename Tag>
+__device__ __forceinline__ uint32_t delta_pair(uint32_t byte);
+template <>
+__device__ __forceinline__ uint32_t delta_pair<f16_tag>(uint32_t byte) {
+  const uint32_t w = (byte & 0xfu) | ((byte & 0xf0u) << 12) | 0x64006400u;       // 1024 + c, twice
+  const f16x2_t bias = {(_Float16)1032.0f, (_Float16)1032.0f};
+  const f16x2_t v = as_f16x2(w) - bias;
+  return __builtin_bit_cast(uint32_t, v);
+}
+template <>
+__device__ __forceinline__ uint32_t delta_pair<bf16_tag>(uint32_t byte) {
+  const uint32_t w = (byte & 0xfu) | ((byte & 0xf0u) << 12) | 0x43004300u;       // 128 + c, twice
+  const float lo = as_f32(w << 16) - 136.0f, hi = as_f32(w & 0xffff0000u) - 136.0f;   // integers in [-8, 7]: the low
+  return (as_u32(lo) >> 16) | (as_u32(hi) & 0xffff0000u);                             // 16 bits of both are zero
+}
+
+// the 8 dense 16-bit values of two groups: `codes16` = their two code bytes, `meta8` = their two meta nibbles
+template <typename Tag>
+__device__ __forceinline__ u32x4 delta_expand(uint32_t codes16, uint32_t meta8) {
+  u32x4 o;
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const uint32_t v = delta_pair<Tag>((codes16 >> (8 * g)) & 0xffu);
+    const uint32_t m = meta8 >> (4 * g);
+    const uint64_t z = ((uint64_t)(v & 0xffffu) << ((m & 3u) * 16)) | ((uint64_t)(v >> 16) << (((m >> 2) & 3u) * 16));
+    o[2 * g] = (uint32_t)z;
+    o[2 * g + 1] = (uint32_t)(z >> 32);
+  }
+  return o;
+}
+
+struct DeltaArgs {
+  char* y;                        // [T, >= N] in dtype, updated in place
+  const char* x;                  // [T, >= K] in dtype
+  const char* codes;              // [slots][N, K / 4] bytes
+  const char* meta;               // [slots][N, K / 8] bytes
+  const char* scales;             // [slots][N] in dtype
+  const int32_t* offsets;
+  const int32_t* sorted_rows;
+  int T, S, N, K;
+  int64_t x_stride, y_stride, codes_slot_stride, meta_slot_stride, scales_slot_stride;   // elements (bytes for the packed two)
+};
+
+template <typename Tag>
+__global__ __launch_bounds__(kDeltaWaves * 64) void delta_mm_kernel(DeltaArgs p) {
+  typedef Elem<Tag> E_;
+  __shared__ float red[kDeltaWaves][kDeltaMB][16 * 17];
+  __shared__ int s_row[kDeltaBM];
+  __shared__ int s_loc[3];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  // (slot, first row, end of the slot's rows) of row block blockIdx.x, or none
+  if (wave == 0) {
+    const int blk = blockIdx.x;
+    int b = 0, en = 0, nb = 0;
+    if (lane < p.S) {
+      b = min(max(p.offsets[lane], 0), p.T);
+      en = min(max(p.offsets[lane + 1], b), p.T);
+      nb = (en - b + kDeltaBM - 1) / kDeltaBM;
+    }
+    int incl = nb;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += o;
+    }
+    const unsigned long long m = __ballot(lane < p.S && blk < incl);
+    if (m == 0) {
+      if (lane == 0) s_loc[0] = -1;
+    } else if (lane == __ffsll((long long)m) - 1) {         // the first such slot has rows
+      s_loc[0] = lane;
+      s_loc[1] = b + (blk - (incl - nb)) * kDeltaBM;
+      s_loc[2] = en;
+    }
+  }
+  __syncthreads();
+  const int slot = s_loc[0];
+  if (slot < 0) return;
+  const int row0 = s_loc[1], row_end = s_loc[2];
+  if (tid < kDeltaBM) {
+    int row = -1;
+    if (row0 + tid < row_end) {
+      row = p.sorted_rows[row0 + tid];
+      if ((unsigned)row >= (unsigned)p.T) row = -1;
+    }
+    s_row[tid] = row;
+  }
+  __syncthreads();
+  const int r16 = lane & 15, q = lane >> 4;
+  const int n0 = blockIdx.y * 16;
+  const int64_t n = n0 + r16;                               // N % 16 == 0: in range
+  const char* cp = p.codes + (int64_t)slot * p.codes_slot_stride + n * (p.K / 4) + 16 * q;
+  const char* mp = p.meta + (int64_t)slot * p.meta_slot_stride + n * (p.K / 8) + 8 * q;
+  const char* xp[kDeltaMB];
+  bool valid[kDeltaMB];
+#pragma unroll
+  for (int sb = 0; sb < kDeltaMB; ++sb) {
+    const int row = s_row[16 * sb + r16];
+    valid[sb] = row >= 0;
+    xp[sb] = p.x + ((int64_t)max(row, 0) * p.x_stride + 64 * q) * 2;
+  }
+  const int chunks = p.K / 64;                              // 64 dense columns each
+  const int steps = (chunks + 3) / 4;
+  f32x4_d acc[kDeltaMB];
+#pragma unroll
+  for (int sb = 0; sb < kDeltaMB; ++sb) acc[sb] = f32x4_d{0.f, 0.f, 0.f, 0.f};
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  for (int ss = wave; ss < steps; ss += kDeltaWaves) {
+    const bool live = 4 * ss + q < chunks;                  // this lane's 64 columns lie below K
+    u32x4 c = {0x88888888u, 0x88888888u, 0x88888888u, 0x88888888u};     // code 8: the value 0
+    u32x2 m = {0x44444444u, 0x44444444u};                               // p0 = 0, p1 = 1
+    if (live) {
+      c = ld16(cp + (int64_t)ss * 64);
+      m = *(const u32x2*)(mp + (int64_t)ss * 32);
+    }
+    u32x4 xf[8][kDeltaMB];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+      for (int sb = 0; sb < kDeltaMB; ++sb)
+        xf[j][sb] = (live && valid[sb]) ? ld16(xp[sb] + (int64_t)ss * 512 + 16 * j) : zero;
+    const uint32_t cw[4] = {c[0], c[1], c[2], c[3]};
+    const uint32_t mw[2] = {m[0], m[1]};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const u32x4 a = delta_expand<Tag>(cw[j >> 1] >> (16 * (j & 1)), mw[j >> 2] >> (8 * (j & 3)));
+#pragma unroll
+      for (int sb = 0; sb < kDeltaMB; ++sb) acc[sb] = mfma_d<Tag>(a, xf[j][sb], acc[sb]);
+    }
+  }
+  // acc[sb][r] = partial of (row 16 sb + r16 of the block, delta row n0 + 4 q + r)
+#pragma unroll
+  for (int sb = 0; sb < kDeltaMB; ++sb)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][sb][(4 * q + r) * 17 + r16] = acc[sb][r];
+  __syncthreads();
+  for (int idx = tid; idx < kDeltaBM * 16; idx += kDeltaWaves * 64) {
+    const int mrow = idx >> 4, col = idx & 15;
+    const int row = s_row[mrow];
+    if (row < 0) continue;
+    float s = red[0][mrow >> 4][col * 17 + (mrow & 15)];
+#pragma unroll
+    for (int w = 1; w < kDeltaWaves; ++w) s = __fadd_rn(s, red[w][mrow >> 4][col * 17 + (mrow & 15)]);
+    const float sc = E_::load(p.scales, (int64_t)slot * p.scales_slot_stride + n0 + col);
+    const int64_t yi = (int64_t)row * p.y_stride + n0 + col;
+    E_::store(p.y, yi, __fadd_rn(E_::load(p.y, yi), __fmul_rn(sc, s)));
+  }
+}
+
+}  // namespace sp
+
+static int delta_shape_status(int64_t num_tokens, int num_slots) {
+  if (num_slots == 0 || num_slots > sp::kDeltaMaxSlots || num_tokens > sp::kDeltaMaxTokens) return SP_ERR_UNSUPPORTED;
+  return SP_OK;
+}
+
+extern "C" int sp_delta_group(int32_t* slot_offsets, int32_t* sorted_rows, const int32_t* indices, int64_t num_tokens,
+                              int num_slots, void* stream) {
+  SP_CHECK_ARG(num_tokens >= 0 && num_slots >= 0);
+  SP_CHECK_ARG(slot_offsets && sorted_rows && indices);
+  if (const int st = delta_shape_status(num_tokens, num_slots)) return st;
+  // (num_tokens == 0 still launches: slot_offsets has to read all zero for whoever looks at it)
+  sp::delta_group_kernel<<<1, sp::kDeltaSortThreads, 0, (hipStream_t)stream>>>(slot_offsets, sorted_rows, indices,
+                                                                               (int)num_tokens, num_slots);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+extern "C" int sp_delta_mm(void* y, const void* x, const void* codes, const void* meta, const void* scales,
+                           const int32_t* slot_offsets, const int32_t* sorted_rows, int64_t num_tokens, int num_slots,
+                           int N, int K, int64_t x_stride, int64_t y_stride, int64_t codes_slot_stride,
+                           int64_t meta_slot_stride, int64_t scales_slot_stride, int dtype, void* stream) {
+  SP_CHECK_ARG(num_tokens >= 0 && num_slots >= 0 && N >= 0 && K >= 0);
+  SP_CHECK_ARG(y && x && codes && meta && scales && slot_offsets && sorted_rows);
+  if (num_tokens == 0) return SP_OK;
+  if (dtype != SP_BF16 && dtype != SP_F16) return SP_ERR_UNSUPPORTED;
+  if (const int st = delta_shape_status(num_tokens, num_slots)) return st;
+  if (K == 0 || K % 64 != 0 || N == 0 || N % 16 != 0 || N / 16 > 65535) return SP_ERR_UNSUPPORTED;
+  SP_CHECK_ARG(x_stride >= K && y_stride >= N && scales_slot_stride >= N);
+  SP_CHECK_ARG(codes_slot_stride >= (int64_t)N * (K / 4) && meta_slot_stride >= (int64_t)N * (K / 8));
+  SP_CHECK_ARG(x_stride % 8 == 0 && codes_slot_stride % 16 == 0 && meta_slot_stride % 8 == 0);
+  SP_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)codes & 15) == 0 && ((uintptr_t)meta & 7) == 0);
+  SP_CHECK_ARG(((uintptr_t)y & 1) == 0 && ((uintptr_t)scales & 1) == 0);
+  const int T = (int)num_tokens;
+  sp::DeltaArgs p{(char*)y, (const char*)x, (const char*)codes, (const char*)meta, (const char*)scales, slot_offsets,
+                  sorted_rows, T, num_slots, N, K, x_stride, y_stride, codes_slot_stride, meta_slot_stride,
+                  scales_slot_stride};
+  const dim3 grid((unsigned)((T + sp::kDeltaBM - 1) / sp::kDeltaBM + num_slots), (unsigned)(N / 16));
+  if (dtype == SP_BF16) sp::delta_mm_kernel<sp::bf16_tag><<<grid, sp::kDeltaWaves * 64, 0, (hipStream_t)stream>>>(p);
+  else sp::delta_mm_kernel<sp::f16_tag><<<grid, sp::kDeltaWaves * 64, 0, (hipStream_t)stream>>>(p);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}

@@ -3,7 +3,7 @@
 Mirrors the hot-path parts of model_executor/model_runner.py (init_memory_pool 360-442,
 init_attention_backend 453-470, forward/forward_decode/forward_extend 506-537, sample 539-563),
 model_executor/cuda_graph_runner.py:144-521 (static-buffer capture / padded replay) and
-managers/tp_worker.py:164-175 (forward_batch_generation, forward_batch_embedding).  LoRA toppings: scratchpad_amd/toppings.py.  Weight
+managers/tp_worker.py:164-175 (forward_batch_generation, forward_batch_embedding).  LoRA and delta toppings: scratchpad_amd/toppings.py.  Weight
 loading, offload, speculative decoding and the NVML/zmq control plane are out of scope.
 """
 import bisect
@@ -197,7 +197,7 @@ class ModelRunner:
                  tp_rank: int = 0, tp_size: int = 1, device: str = "cuda",
                  dtype: torch.dtype = torch.bfloat16, gpu_id: int = 0, seed: int = 0,
                  init_weights: bool = True, toppings: Optional[list] = None):
-        """``toppings``: LoRAAdapter objects (scratchpad_amd/toppings.py) to serve; with
+        """``toppings``: LoRAAdapter objects or DeltaAdapter objects (scratchpad_amd/toppings.py) to serve; with
         ``server_args.max_toppings_per_batch`` they build the ToppingsManager, which wraps the target projections
         (before or after the weights are loaded: ``load_full_state_dict`` / ``load_weights`` see through the wrappers).
         One without the other is refused.  An extend batch may carry ``server_args.max_prefill_tokens`` tokens."""
@@ -383,7 +383,8 @@ class ModelRunner:
                 and self.graph_runner.can_run(forward_batch)):
             return self.graph_runner.replay(forward_batch)
         if self.topping_manager is not None and self.topping_manager.enabled:
-            self.topping_manager.prepare_topping_batch(forward_batch)
+            rows = self.topping_manager.prepare_topping_batch(forward_batch)
+            self.topping_manager.group_topping_batch(rows.shape[0])      # (delta adapters: the rows sorted by slot)
         if forward_batch.forward_mode.is_decode():
             return self.forward_decode(forward_batch)
         if forward_batch.forward_mode.is_extend():
@@ -511,7 +512,13 @@ class HipGraphRunner:
         mr.attn_backend.init_forward_metadata_capture_cuda_graph(
             bs, bs, fb.req_pool_indices, fb.seq_lens, enc, ForwardMode.DECODE, None)
 
+        tm = mr.topping_manager if mr.topping_manager is not None and mr.topping_manager.enabled else None
+
         def run_once():
+            if tm is not None:
+                # delta adapters: the grouping of the bucket's rows is part of the captured step, ahead of the first
+                # layer - a replay sorts whatever the index buffer holds by then
+                tm.group_topping_batch(bs)
             return mr.model.forward(fb.input_ids, fb.positions, fb)
 
         # warm up on a side stream before capturing (cuda_graph_runner.py:400-412)

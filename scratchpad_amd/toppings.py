@@ -1,15 +1,23 @@
-"""LoRA toppings: many fine-tuned variants of one base model served from one engine.
+"""Toppings: many fine-tuned variants of one base model served from one engine, as LoRA adapters or as compressed
+full-model deltas.
 
-Re-hosts nn/toppings/topping_module.py (LoRAAdapter 121-181), nn/toppings/topping_layer.py (28-391),
-memory/topping_pool.py (35-124) and managers/toppings_manager.py (76-592) for LoRA adapters on Llama at TP = 1.  The
-reference hands the arithmetic to triteia.python.ops.ldmm (not part of its tree); here it is ``sp_lora_shrink`` /
-``sp_lora_expand`` (csrc/lora.hip): per projection one shrink and one expand (two for qkv), whatever the number of
-adapters in the batch, every row choosing its adapter by an int32 slot index (-1: base model only).
+Re-hosts nn/toppings/topping_module.py (DeltaAdapter 68-118, LoRAAdapter 121-181), nn/toppings/topping_layer.py
+(28-391), memory/topping_pool.py (35-172) and managers/toppings_manager.py (76-592) on Llama at TP = 1.  The reference
+hands the arithmetic to triteia.python.ops.ldmm (not part of its tree); here it is
 
-Refused, each with a NotImplementedError that names it: delta toppings (deltazip-packed weights, DeltaAdapter, the
-qweight / meta / scales buffers), embedding and LM-head swaps, TP > 1.
+* LoRA: ``sp_lora_shrink`` / ``sp_lora_expand`` (csrc/lora.hip): per projection one shrink and one expand (two for
+  qkv), whatever the number of adapters in the batch, every row choosing its adapter by an int32 slot index (-1: base
+  model only);
+* delta (W_finetuned - W_base stored 4-bit and 2:4 sparse, scratchpad_amd/delta.py): ``sp_delta_group`` once per
+  forward (the rows of the index vector sorted by slot, on the device) and ONE ``sp_delta_mm`` per wrapped projection
+  over its whole stacked output (csrc/delta.hip): 4 launches per layer.
 
-Nothing here reads files or the network: an adapter is built from a state dict of tensors with PEFT names.
+A manager serves LoRA adapters or delta adapters, not both.  Refused, each with a NotImplementedError that names it:
+the two kinds in one manager, a delta topping no DeltaAdapter object was handed in for (loading one from a path), the
+reference's triteia-layout (qweight, meta, scales) triple as a raw tuple, compress configs other than 4 bit / 2:4,
+delta tensors outside the decoder layers' projections (embedding, LM-head and norm swaps), TP > 1.
+
+Nothing here reads files or the network: an adapter is built from a state dict of tensors.
 """
 import re
 from typing import Dict, Iterable, List, Optional, Tuple
@@ -18,6 +26,7 @@ import torch
 from torch import nn
 
 from . import _native
+from .delta import ZERO_CODE, ZERO_META, empty_delta
 from .llama import MergedColumnParallelLinear, QKVParallelLinear, RowParallelLinear, _ShardedLinear
 
 
@@ -134,18 +143,140 @@ class LoRAAdapter:
             layer.weights[template.replace(f".{first}.", f".{stacked}.")] = torch.cat(tensors, 0)
 
 
+class DeltaBuffer:
+    """What ``set_topping_info(delta_buffer=...)`` takes: the packed delta slots of ONE projection of one layer in this
+    library's layout (scratchpad_amd/delta.py) - codes uint8 [slots, N, K / 4], meta uint8 [slots, N, K / 8], scales
+    [slots, N].  Not a tuple on purpose: a raw tuple is the reference's triteia-layout triple, which is refused."""
+    __slots__ = ("codes", "meta", "scales")
+
+    def __init__(self, codes: torch.Tensor, meta: torch.Tensor, scales: torch.Tensor):
+        if codes.dim() != 3 or meta.dim() != 3 or scales.dim() != 2 or codes.dtype != torch.uint8 \
+                or meta.dtype != torch.uint8 or codes.shape[:2] != meta.shape[:2] or codes.shape[:2] != scales.shape \
+                or codes.shape[2] != 2 * meta.shape[2]:
+            raise ValueError("DeltaBuffer: codes uint8 [slots, N, K / 4], meta uint8 [slots, N, K / 8], scales "
+                             f"[slots, N]; got {tuple(codes.shape)}, {tuple(meta.shape)}, {tuple(scales.shape)}")
+        self.codes, self.meta, self.scales = codes, meta, scales
+
+
+_DELTA_PROJ = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+_DELTA_STACKS = {"qkv_proj": ("q_proj", "k_proj", "v_proj"), "gate_up_proj": ("gate_proj", "up_proj")}
+_DELTA_MEMBERS = ("codes", "meta", "scales")
+
+
+def delta_proj_shape(proj: str, cfg) -> Tuple[int, int]:
+    """(output rows N, input width K) of one HF projection's dense delta"""
+    D = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
+    q, kv = cfg.num_attention_heads * D, cfg.num_key_value_heads * D
+    return {"q_proj": (q, cfg.hidden_size), "k_proj": (kv, cfg.hidden_size), "v_proj": (kv, cfg.hidden_size),
+            "o_proj": (cfg.hidden_size, q), "gate_proj": (cfg.intermediate_size, cfg.hidden_size),
+            "up_proj": (cfg.intermediate_size, cfg.hidden_size),
+            "down_proj": (cfg.hidden_size, cfg.intermediate_size)}[proj]
+
+
+def delta_module_shape(module: str, cfg) -> Tuple[int, int]:
+    """(N, K) of a model module's delta: the stacked rows of its projections"""
+    parts = _DELTA_STACKS.get(module, (module,))
+    return sum(delta_proj_shape(p, cfg)[0] for p in parts), delta_proj_shape(parts[0], cfg)[1]
+
+
+class DeltaAdapter:
+    """topping_module.py:68-118.  ``initialize_weights(state_dict)`` takes the packed tensors of scratchpad_amd/delta.py
+    under ``...layers.N.self_attn.q_proj.codes`` / ``.meta`` / ``.scales`` (and k_proj, v_proj, o_proj, mlp.gate_proj,
+    up_proj, down_proj) and stacks q|k|v and gate|up by rows - the format is row-local, so stacking is concatenation.
+    A projection of a stacked group the adapter does not carry enters the stack as zeros (code 8, scale 1).
+    ``layers[i].weights`` is keyed by the name behind ``layers.i.`` with the module name of the model
+    (``self_attn.qkv_proj.codes``)."""
+
+    def __init__(self, uid, config: ToppingConfig, base_hf_config, load_config=None):
+        self.uid = uid
+        self.config = config
+        self.base_hf_config = base_hf_config
+        self.load_config = load_config
+        cc = dict(config.hf_config.get("compress_config") or {"bits": 4, "sparsity": 0.5})
+        if cc.get("bits", 4) != 4 or cc.get("sparsity", 0.5) != 0.5:
+            raise NotImplementedError(f"delta compress_config {cc}: only bits = 4, sparsity = 0.5 (2:4) deltas are "
+                                      "served (2-bit and dense deltas are out of scope)")
+        self.pack_factor = 32 // 4
+        self.sparse_factor = 2
+        self.layers = [ToppingLayer() for _ in range(base_hf_config.num_hidden_layers)]
+        self.target_modules: set = set()       # the model modules this adapter carries a delta for
+
+    def get_stacked_multiply_delta(self, module_name: str) -> int:
+        return {"kv_proj": 2, "gate_up_proj": 2, "qkv_proj": 3}.get(module_name, 1)
+
+    def get_pack_factor(self) -> int:
+        return self.pack_factor
+
+    def get_sparse_factor(self) -> int:
+        return self.sparse_factor
+
+    def initialize_weights(self, state_dict: Optional[Dict[str, torch.Tensor]] = None) -> "DeltaAdapter":
+        if state_dict is None:
+            raise NotImplementedError("DeltaAdapter loads from a state dict of packed tensors: reading deltazip "
+                                      "checkpoints from files or the network is out of scope")
+        cfg = self.base_hf_config
+        found: List[Dict[str, Dict[str, torch.Tensor]]] = [dict() for _ in self.layers]
+        for name, w in state_dict.items():
+            lid = get_layer_id(name)
+            m = re.search(r"layers\.\d+\.((?:self_attn|mlp)\.(\w+))\.(\w+)$", name)
+            if lid is None or m is None or m.group(2) not in _DELTA_PROJ:
+                raise NotImplementedError(f"delta tensor {name!r}: only the decoder layers' projections {_DELTA_PROJ} "
+                                          "take a delta (embed_tokens, lm_head and norm swaps - the reference's "
+                                          "outside_layer_modules / uncompressed_delta_target_weights - are out of "
+                                          "scope)")
+            if m.group(3) not in _DELTA_MEMBERS:
+                raise NotImplementedError(f"delta tensor {name!r}: a projection carries codes, meta and scales (the "
+                                          "reference's triteia-layout qweight / metas are not converted)")
+            if not 0 <= lid < len(self.layers):
+                raise ValueError(f"{name}: the model has {len(self.layers)} layers")
+            found[lid].setdefault(m.group(2), {})[m.group(3)] = w.detach().cpu()
+        for lid, projs in enumerate(found):
+            for proj, members in projs.items():
+                N, K = delta_proj_shape(proj, cfg)
+                want = {"codes": (N, K // 4), "meta": (N, K // 8), "scales": (N,)}
+                for k in _DELTA_MEMBERS:
+                    if k not in members:
+                        raise ValueError(f"layer {lid} {proj}: {k} is missing")
+                    if tuple(members[k].shape) != want[k]:
+                        raise ValueError(f"layer {lid} {proj}.{k}: {tuple(members[k].shape)}, expected {want[k]}")
+                    if k != "scales" and members[k].dtype != torch.uint8:
+                        raise ValueError(f"layer {lid} {proj}.{k}: uint8 expected, got {members[k].dtype}")
+            for module, block in (("qkv_proj", "self_attn"), ("o_proj", "self_attn"), ("gate_up_proj", "mlp"),
+                                  ("down_proj", "mlp")):
+                parts = _DELTA_STACKS.get(module, (module,))
+                if not any(p in projs for p in parts):
+                    continue
+                dtype = next(projs[p]["scales"].dtype for p in parts if p in projs)
+                stack = [projs[p] if p in projs else dict(zip(_DELTA_MEMBERS, empty_delta(*delta_proj_shape(p, cfg), dtype)))
+                         for p in parts]
+                for k in _DELTA_MEMBERS:
+                    self.layers[lid].weights[f"{block}.{module}.{k}"] = torch.cat([s[k] for s in stack], 0).contiguous()
+                self.target_modules.add(module)
+        return self
+
+
 class ToppingMemPool:
     """topping_pool.py:35-124, the LoRA half: ``A_buffer[module][layer]`` is [slots, in, r * c] and
     ``B_buffer[module][layer]`` is [slots, r, out * c] (c = stacked slices of the module), in the model dtype,
     allocated ONCE and zeroed: every address a captured graph holds stays valid, and an unloaded slot adds 0.
     The layers of a module are views of one [layers, slots, ., .] allocation (``A_all`` / ``B_all``), so that
-    loading an adapter into a slot is one copy per module."""
+    loading an adapter into a slot is one copy per module.
+
+    topping_pool.py:126-172, the delta half (``deltas`` given): per model module of ``delta_target_weights`` ONE
+    allocation each for codes, meta and scales - ``qweight_all[module]`` uint8 [layers, slots, N, K / 4],
+    ``meta_all[module]`` uint8 [layers, slots, N, K / 8], ``scales_all[module]`` [layers, slots, N] in the model dtype -
+    with per-layer views ``qweight_buffer`` / ``meta_buffer`` / ``scales_buffer`` [module][layer] (the reference's
+    names; the layout is this library's, scratchpad_amd/delta.py).  Allocated once; an empty slot holds code 8 and
+    scale 1 and adds exactly 0."""
 
     def __init__(self, args, base_hf_config, loras: List[LoRAAdapter], target_weights, max_toppings_per_batch: int,
                  max_lora_dim: int, base_model=None, lora_dtype: torch.dtype = torch.bfloat16, device="cuda",
                  deltas=None, delta_target_weights=None, uncompressed_delta_target_weights=None):
-        if deltas:
-            raise NotImplementedError("delta toppings (deltazip-packed weights) are out of scope")
+        if uncompressed_delta_target_weights:
+            raise NotImplementedError("uncompressed delta target weights (embedding / LM-head / norm swaps) are out of "
+                                      "scope")
+        if deltas and loras:
+            raise NotImplementedError("LoRA and delta toppings in one pool are out of scope")
         self.args = args
         self.base_model = base_model
         self.base_hf_config = base_hf_config
@@ -172,6 +303,32 @@ class ToppingMemPool:
                 self.B_all[module_B] = torch.zeros((num_layers, max_toppings_per_batch, max_lora_dim, dim_B * c),
                                                    dtype=lora_dtype, device=device)
                 self.B_buffer[module_B] = list(self.B_all[module_B].unbind(0))
+        self.deltas = list(deltas or [])
+        self.delta_target_weights = sorted(delta_target_weights or []) if self.deltas else []
+        self.qweight_all: Dict[str, torch.Tensor] = {}
+        self.meta_all: Dict[str, torch.Tensor] = {}
+        self.scales_all: Dict[str, torch.Tensor] = {}
+        self.qweight_buffer: Dict[str, List[torch.Tensor]] = {}
+        self.meta_buffer: Dict[str, List[torch.Tensor]] = {}
+        self.scales_buffer: Dict[str, List[torch.Tensor]] = {}
+        for module in self.delta_target_weights:
+            N, K = delta_module_shape(module, base_hf_config)
+            if K % 64 != 0 or N % 16 != 0:
+                raise NotImplementedError(f"delta toppings on {module} [{N}, {K}]: sp_delta_mm serves input widths "
+                                          "that are multiples of 64 and output widths that are multiples of 16")
+            shape = (num_layers, max_toppings_per_batch, N)
+            self.qweight_all[module] = torch.full(shape + (K // 4,), ZERO_CODE, dtype=torch.uint8, device=device)
+            self.meta_all[module] = torch.full(shape + (K // 8,), ZERO_META, dtype=torch.uint8, device=device)
+            self.scales_all[module] = torch.ones(shape, dtype=lora_dtype, device=device)
+            self.qweight_buffer[module] = list(self.qweight_all[module].unbind(0))
+            self.meta_buffer[module] = list(self.meta_all[module].unbind(0))
+            self.scales_buffer[module] = list(self.scales_all[module].unbind(0))
+
+    def delta_buffer(self, module: str, layer_id: int) -> Optional[DeltaBuffer]:
+        if module not in self.qweight_buffer:
+            return None
+        return DeltaBuffer(self.qweight_buffer[module][layer_id], self.meta_buffer[module][layer_id],
+                           self.scales_buffer[module][layer_id])
 
 
 # --------------------------------------------------------------------------- layers
@@ -187,6 +344,8 @@ class BaseLayerWithTopping(nn.Module):
         self.set_topping = False
         self.weight_indices = None
         self.scaling = 1.0
+        self.delta: Optional[DeltaBuffer] = None
+        self.delta_groups = None
 
     @property
     def weight(self):
@@ -199,10 +358,25 @@ class BaseLayerWithTopping(nn.Module):
         ...
 
     @staticmethod
-    def _no_delta(**buffers) -> None:
-        for name, b in buffers.items():
-            if b is not None:
-                raise NotImplementedError(f"delta toppings are out of scope ({name} must be None)")
+    def _delta(name: str, b) -> Optional[DeltaBuffer]:
+        if b is None or isinstance(b, DeltaBuffer):
+            return b
+        raise NotImplementedError(f"delta toppings: {name} must be a DeltaBuffer (codes, meta, scales in this library's "
+                                  "layout) or None; a raw tuple is the reference's triteia-layout triple, whose "
+                                  "conversion is out of scope")
+
+    def _set_delta(self, delta: Optional[DeltaBuffer], delta_groups) -> None:
+        """the packed slots of this projection and the manager's persistent (slot_offsets, sorted_rows)"""
+        if delta is not None and delta_groups is None:
+            raise ValueError("a delta_buffer goes with delta_groups = (slot_offsets, sorted_rows)")
+        self.delta = delta
+        self.delta_groups = tuple(delta_groups) if delta is not None else None
+
+    def _add_packed_delta(self, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """out += x . delta[slot of the row]^T over the whole (stacked) output: ONE launch"""
+        d = self.delta
+        _native.delta_mm(out, x, d.codes, d.meta, d.scales, self.delta_groups[0], self.delta_groups[1])
+        return out
 
     def _tokens(self, x: torch.Tensor) -> torch.Tensor:
         if self.weight_indices is None:
@@ -214,8 +388,9 @@ class ColumnParallelLinearWithTopping(BaseLayerWithTopping):
     """topping_layer.py:73-108: out += (x . A[idx]) . B[idx], one shrink and one expand in place on the base output"""
     num_slices = 1
 
-    def set_topping_info(self, bs, weight_indices, lora_buffer=None, delta_buffer=None, scaling=None):
-        self._no_delta(delta_buffer=delta_buffer)
+    def set_topping_info(self, bs, weight_indices, lora_buffer=None, delta_buffer=None, scaling=None,
+                         delta_groups=None):
+        self._set_delta(self._delta("delta_buffer", delta_buffer), delta_groups)
         self.weight_indices = weight_indices
         self.A_buffer, self.B_buffer = (None, None) if lora_buffer is None else (lora_buffer[0], lora_buffer[1])
         if scaling is not None:
@@ -223,6 +398,8 @@ class ColumnParallelLinearWithTopping(BaseLayerWithTopping):
         self.set_topping = True
 
     def _add_delta(self, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        if self.delta is not None:
+            self._add_packed_delta(x, out)
         if self.A_buffer is None or self.B_buffer is None:
             return out
         idx = self._tokens(x)
@@ -245,8 +422,14 @@ class QKVParallelLinearWithToppings(ColumnParallelLinearWithTopping):
     two kv slices (tmp offset by r, the output offset by the q width)"""
 
     def set_topping_info(self, bs, weight_indices, lora_buffer=None, delta_buffer_q=None, delta_buffer_kv=None,
-                         scaling=None):
-        self._no_delta(delta_buffer_q=delta_buffer_q, delta_buffer_kv=delta_buffer_kv)
+                         scaling=None, delta_groups=None):
+        """``delta_buffer_q``: the DeltaBuffer of the whole stacked q|k|v output (one launch); the reference's separate
+        kv triple has no counterpart, so ``delta_buffer_kv`` stays None"""
+        q = self._delta("delta_buffer_q", delta_buffer_q)
+        if self._delta("delta_buffer_kv", delta_buffer_kv) is not None:
+            raise NotImplementedError("delta toppings: q|k|v is ONE stacked delta_buffer_q here; a separate "
+                                      "delta_buffer_kv is not served")
+        self._set_delta(q, delta_groups)
         self.weight_indices = weight_indices
         self.A_buffer_qkv, self.B_buffer_q, self.B_buffer_kv = (None, None, None) if lora_buffer is None else lora_buffer
         if scaling is not None:
@@ -255,6 +438,8 @@ class QKVParallelLinearWithToppings(ColumnParallelLinearWithTopping):
 
     def forward(self, input_: torch.Tensor):
         out = self.base_layer(input_)[0]
+        if self.delta is not None:
+            self._add_packed_delta(input_, out)
         if self.A_buffer_qkv is None:
             return out, None
         idx = self._tokens(input_)
@@ -275,9 +460,10 @@ class RowParallelLinearWithTopping(ColumnParallelLinearWithTopping):
     """topping_layer.py:244-294, keeping this project's ``reduce_output`` (TP = 1: there is nothing to reduce; the
     delta is added to this rank's output before the base layer would have reduced it, so TP > 1 is refused)"""
 
-    def set_topping_info(self, bs, weight_indices, lora_buffer=None, delta_buffer=None, debug=False, scaling=None):
+    def set_topping_info(self, bs, weight_indices, lora_buffer=None, delta_buffer=None, debug=False, scaling=None,
+                         delta_groups=None):
         super().set_topping_info(bs, weight_indices, lora_buffer=lora_buffer, delta_buffer=delta_buffer,
-                                 scaling=scaling)
+                                 scaling=scaling, delta_groups=delta_groups)
 
     def forward(self, input_: torch.Tensor, reduce_output: bool = True):
         if getattr(self.base_layer, "tp_size", 1) > 1:
@@ -308,11 +494,17 @@ def replace_submodule(model: nn.Module, module_name: str, new_module: nn.Module)
 
 # --------------------------------------------------------------------------- manager
 class ToppingsManager:
-    """managers/toppings_manager.py:76-592 for LoRA adapters.
+    """managers/toppings_manager.py:76-592 for LoRA adapters or for delta adapters (one kind per manager).
 
-    ``adapters``: LoRAAdapter objects whose weights are loaded (this takes the place of ``server_args.init_toppings``
-    and the checkpoint loader).  Without adapters, or with ``max_toppings_per_batch`` unset, the manager is disabled
-    and touches nothing.  All registered adapters share ``r`` and ``scaling`` (toppings_manager.py:208-213).
+    ``adapters``: LoRAAdapter objects, or DeltaAdapter objects, whose weights are loaded (this takes the place of
+    ``server_args.init_toppings`` and the checkpoint loader).  Without adapters, or with ``max_toppings_per_batch``
+    unset, the manager is disabled and touches nothing.  All registered LoRA adapters share ``r`` and ``scaling``
+    (toppings_manager.py:208-213).
+
+    Delta adapters: next to ``weight_indices`` the manager owns the persistent ``slot_offsets`` [slots + 1] and
+    ``sorted_rows`` buffers every topping layer holds.  ``group_topping_batch(num_tokens)`` fills them with ONE
+    ``sp_delta_group`` launch from the device index buffer alone: eagerly behind ``prepare_topping_batch``, and inside
+    the captured region ahead of the first layer under the graph runner, so a replay follows a changed index vector.
 
     Three deliberate deviations from the reference's ``prepare_topping_batch``:
       * LoRA is not asserted away (the reference: ``assert len_loras == 0, "LoRA is not supported in this version"``);
@@ -337,6 +529,11 @@ class ToppingsManager:
             return
         if tp_size > 1:
             raise NotImplementedError("toppings under tensor parallelism (TP > 1) are out of scope")
+        kinds = {isinstance(a, DeltaAdapter) for a in adapters}
+        if len(kinds) > 1:
+            raise NotImplementedError("LoRA and delta toppings in one manager are out of scope: a manager serves "
+                                      "LoRAAdapter objects or DeltaAdapter objects")
+        self.kind = "delta" if kinds == {True} else "lora"
         self.enabled = True
         p = next(iter(base_model.parameters()), None)
         self.device = device if device is not None else (p.device if p is not None else "cpu")
@@ -351,14 +548,26 @@ class ToppingsManager:
         # one entry per token of the largest step; -1 = base model only
         n = max_tokens or max(getattr(server_args, "max_prefill_tokens", 16384), 1)
         self.weight_indices = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+        # the grouping of the step's rows by slot (delta adapters): rewritten by every group_topping_batch
+        self.slot_offsets = self.sorted_rows = None
+        if self.kind == "delta":
+            self.slot_offsets = torch.zeros((self.max_toppings_per_batch + 1,), dtype=torch.int32, device=self.device)
+            self.sorted_rows = torch.zeros((n,), dtype=torch.int32, device=self.device)
         self._wire_modules()
 
     # ---- set-up
     def register_topping(self, topping_type, topping_path: str, topping_name: str) -> None:
-        if str(getattr(topping_type, "value", topping_type)) == "delta":
-            raise NotImplementedError("delta toppings (deltazip-packed weights) are out of scope: LoRA only")
-        if str(getattr(topping_type, "value", topping_type)) != "lora":
+        kind = str(getattr(topping_type, "value", topping_type))
+        if kind not in ("lora", "delta"):
             raise NotImplementedError(f"unknown topping type {topping_type!r}")
+        adapter = getattr(self, "_adapters", {}).get(topping_name)
+        if kind == "delta" and not isinstance(adapter, DeltaAdapter):
+            raise NotImplementedError(f"delta topping {topping_name!r}: no DeltaAdapter object was handed to the "
+                                      "manager for it; loading a deltazip checkpoint from a path is out of scope")
+        if kind != getattr(self, "kind", kind) or (kind == "lora" and isinstance(adapter, DeltaAdapter)):
+            raise NotImplementedError(f"topping {topping_name!r} is registered as {kind!r} with a manager of "
+                                      f"{getattr(self, 'kind', 'another kind')!r} adapters: LoRA and delta toppings "
+                                      "in one manager are out of scope")
         self.available_toppings[topping_name] = (topping_type, topping_path)
 
     def init_topping_batch(self) -> None:
@@ -367,6 +576,28 @@ class ToppingsManager:
 
     def init_toppings(self) -> None:
         self.configs = {name: self._adapters[name].config for name in self.available_toppings}
+        self.loras: List[LoRAAdapter] = []
+        self.lora_id: Dict[str, int] = {}
+        self.deltas: List[DeltaAdapter] = []
+        self.delta_id: Dict[str, int] = {}
+        if self.kind == "delta":
+            for c in self.configs.values():
+                for m in c.hf_config.get("target_modules", ()):
+                    if m in ("lm_head", "embed_tokens", "logits_processor", "norm"):
+                        raise NotImplementedError(f"toppings on {m} (embedding / LM-head / norm swaps) are out of scope")
+            for name in self.available_toppings:
+                self.delta_id[name] = self.toppings_id[name] = len(self.deltas)
+                self.deltas.append(self._adapters[name])
+            self.target_modules = set().union(*(a.target_modules for a in self.deltas))
+            if not self.target_modules:
+                raise ValueError("the delta adapters carry no tensors (initialize_weights(state_dict) first)")
+            self.origin_target_modules = set(self.target_modules)
+            self.target_weights = set()
+            self.max_lora_dim, self.scaling = 0, 1.0
+            self.topping_modules = []
+            for module_name, module in self.get_target_modules():
+                self.topping_modules.append((module_name, self.set_topping_module(module_name, module)))
+            return
         self.origin_target_modules = set()
         for c in self.configs.values():
             self.origin_target_modules |= set(c.hf_config["target_modules"])
@@ -375,8 +606,6 @@ class ToppingsManager:
                 raise NotImplementedError(f"toppings on {m} (embedding / LM-head swaps) are out of scope")
         self.target_modules = {get_module_name(m) for m in self.origin_target_modules}
         self.target_weights = {get_stacked_name(m) for m in self.origin_target_modules}
-        self.loras: List[LoRAAdapter] = []
-        self.lora_id: Dict[str, int] = {}
         for name in self.available_toppings:
             self.lora_id[name] = self.toppings_id[name] = len(self.loras)
             self.loras.append(self._adapters[name])
@@ -396,7 +625,8 @@ class ToppingsManager:
         self.topping_memory_pool = ToppingMemPool(
             args, base_hf_config=self.base_hf_config, loras=self.loras, target_weights=self.target_weights,
             max_toppings_per_batch=self.max_toppings_per_batch, max_lora_dim=self.max_lora_dim,
-            base_model=self.base_model, lora_dtype=self.dtype, device=self.device)
+            base_model=self.base_model, lora_dtype=self.dtype, device=self.device, deltas=self.deltas,
+            delta_target_weights=self.target_modules if self.kind == "delta" else None)
 
     def set_topping_module(self, module_name: str, module: nn.Module) -> BaseLayerWithTopping:
         return replace_submodule(self.base_model, module_name, get_topping_layer(module))
@@ -418,6 +648,13 @@ class ToppingsManager:
 
     def _wire_modules(self) -> None:
         """hand every topping layer its buffers and THE index tensor, once: nothing a layer holds changes afterwards"""
+        if self.kind == "delta":
+            groups = (self.slot_offsets, self.sorted_rows)
+            for module_name, module in self.topping_modules:
+                buf = self.topping_memory_pool.delta_buffer(module_name.split(".")[-1], get_layer_id(module_name))
+                key = "delta_buffer_q" if "qkv_proj" in module_name else "delta_buffer"
+                module.set_topping_info(0, self.weight_indices, **{key: buf}, delta_groups=groups)
+            return
         A, B = self.A_buffer, self.B_buffer
         for module_name, module in self.topping_modules:
             layer_id = get_layer_id(module_name)
@@ -490,11 +727,63 @@ class ToppingsManager:
             view.copy_(torch.tensor(slots, dtype=torch.int32), non_blocking=True)
         return view
 
+    def group_topping_batch(self, num_tokens: int) -> None:
+        """delta adapters: the first ``num_tokens`` rows of the index buffer grouped by slot, on the device (one
+        launch, no host read: capturable).  Nothing to do for LoRA adapters, whose kernels read the index vector."""
+        if self.enabled and self.kind == "delta":
+            _native.delta_group(self.weight_indices, int(num_tokens), self.max_toppings_per_batch, self.slot_offsets,
+                                self.sorted_rows)
+
     # ---- slots
     def load_topping(self, uid, buffer_id: int) -> None:
         if uid is not None and uid not in self.available_toppings:
             raise KeyError(f"topping {uid!r} is not registered")
-        self._load_lora(uid, buffer_id)
+        if self.kind == "delta":
+            self._load_delta(uid, buffer_id)
+        else:
+            self._load_lora(uid, buffer_id)
+
+    def _delta_pools(self):
+        pool = self.topping_memory_pool
+        return (("codes", pool.qweight_all), ("meta", pool.meta_all), ("scales", pool.scales_all))
+
+    def _stage_delta(self, uid) -> Dict[Tuple[str, str], torch.Tensor]:
+        """adapter ``uid`` as the pool stores it: per module and buffer ONE contiguous [layers, N, .] host tensor
+        (pinned where the pool is on a device); a module or layer the adapter carries nothing for is an empty delta"""
+        if uid in self._staged:
+            return self._staged[uid]
+        staged = {}
+        fill = {"codes": ZERO_CODE, "meta": ZERO_META, "scales": 1}
+        for kind, all_ in self._delta_pools():
+            for module, big in all_.items():
+                t = torch.full((big.shape[0],) + tuple(big.shape[2:]), fill[kind], dtype=big.dtype)
+                staged[(kind, module)] = t.pin_memory() if big.is_cuda else t
+        for i, layer in enumerate(self.deltas[self.delta_id[uid]].layers):
+            for name, w in layer.weights.items():
+                module, kind = name.split(".")[-2:]
+                dst = staged[(kind, module)][i]
+                if tuple(w.shape) != tuple(dst.shape):
+                    raise ValueError(f"layer {i} {name}: {tuple(w.shape)} does not fit the slot {tuple(dst.shape)}")
+                if w.dtype != dst.dtype:      # (a scale converted to another dtype is another delta)
+                    raise ValueError(f"layer {i} {name}: {w.dtype}, the pool holds {dst.dtype}")
+                dst.copy_(w)
+        self._staged[uid] = staged
+        return staged
+
+    def _load_delta(self, uid, buffer_id: int) -> None:
+        """adapter ``uid`` into slot ``buffer_id`` of every layer: one copy per module and buffer from the staged host
+        tensors; ``uid`` None leaves the slot empty (code 8, scale 1: it adds exactly 0).  In place: a captured graph
+        sees the new contents at its next replay."""
+        if not 0 <= buffer_id < self.max_toppings_per_batch:
+            raise IndexError(f"slot {buffer_id} outside [0, {self.max_toppings_per_batch})")
+        staged = None if uid is None else self._stage_delta(uid)
+        fill = {"codes": ZERO_CODE, "meta": ZERO_META, "scales": 1}
+        for kind, all_ in self._delta_pools():
+            for module, big in all_.items():
+                if staged is None:
+                    big[:, buffer_id].fill_(fill[kind])
+                else:
+                    big[:, buffer_id].copy_(staged[(kind, module)], non_blocking=True)
 
     def _stage(self, uid) -> Dict[Tuple[int, str], torch.Tensor]:
         """adapter ``uid`` as the pool stores it: per module ONE contiguous [layers, in, r c] (A) / [layers, r, out c]
