@@ -9,17 +9,13 @@
 // and the dense value is scales[n] * (code - 8).  The lanes of a row read contiguous bytes.
 //
 //   sp_delta_group  the stable counting sort of the rows t with 0 <= indices[t] < slots by slot: slot_offsets[slots + 1],
-//                   sorted_rows[T].  ONE workgroup, moe_sort_kernel's method (csrc/moe.hip): thread i counts the slots
-//                   of the i-th contiguous chunk of rows into its own LDS column, a flat prefix over [slot][thread]
-//                   gives every (slot, thread) its first entry, the thread writes its chunk in order.  No atomic.
+//                   sorted_rows[T]: the shared sort (group_sort.hip)
 //   sp_delta_mm     y[t, n] = round(y[t, n] + scale_s[n] * sum_k x[t, k] * q_s[n, k])  for every sorted row t of slot s
 //
-// The product is moe_gemm_kernel (csrc/moe.hip) with "expert" = slot, top-k = 1 and the weight operand unpacked in
-// registers:
-//   * a workgroup (8 waves) owns kDeltaBM = 32 consecutive sorted rows of ONE slot x 16 rows of that slot's delta;
-//   * grid.x = ceil(T / BM) + slots row blocks, an upper bound computed from (T, slots); wave 0 finds the block's
-//     (slot, first row) from slot_offsets with one wave prefix sum and the workgroup exits if there is none, so a slot
-//     without rows costs no weight traffic;
+// The product is the grouped form of the weight-streaming core of stream_gemm.h with group = slot (geometry, block
+// search, park and sum, batch invariance and the safety rules are stated there) and the weight operand unpacked in
+// registers.  What is its own:
+//   * a workgroup owns 32 consecutive sorted rows of ONE slot x 16 rows of that slot's delta;
 //   * the reduction is cut into super-steps of 256 dense columns, which the 8 waves take round-robin.  In a super-step
 //     lane (r16, q) loads 16 B of codes and 8 B of meta of delta row n0 + r16 - the 64 dense columns 256 ss + 64 q ..
 //     + 63 - and spends them over 8 v_mfma_f32_16x16x32: k-slot (q, i) of MFMA j carries dense column
@@ -29,90 +25,16 @@
 //   * unpacking is VALU: a code byte becomes two 16-bit floats through the exponent trick (0x6400 | c is 1024 + c in
 //     fp16, 0x4300 | c is 128 + c in bf16; subtracting 1032 resp. 136 leaves the integer c - 8 exactly), and the pair is
 //     shifted to the 16-bit positions p0 and p1 of the group's four;
-//   * the waves' partial tiles are summed through LDS in wave order, multiplied by the row's scale, added to y and
-//     rounded once.  Every (t, n) has one writer.
+//   * the epilogue: the sum is multiplied by the row's scale, added to y and rounded once.  Every (t, n) has one writer.
 // The sparse MFMA (v_smfmac_f32_16x16x64) is not used: see DESIGN.md 4.6c.
 //
 // BATCH INVARIANCE: the bits a row receives depend on that row's x and y, its slot's packed delta and (N, K) only.  The
-// super-steps of a wave, the 8 MFMAs inside one and the order over the waves are functions of K alone; a row's position
-// inside its block only selects the lane column of the MFMA, and rows that are absent feed zeros into columns of their
-// own.
-//
-// Safety: every sorted row is checked against [0, T) before an address is formed from it; rows past a slot's end and
-// rows in no group are never loaded or stored; the offsets read from slot_offsets are clamped to [0, T]; all byte
-// offsets are 64-bit.
-#include "sp_common.h"
+// super-steps of a wave, the 8 MFMAs inside one and the order over the waves are functions of K alone (stream_gemm.h).
+#include "stream_gemm.h"
 
 namespace sp {
 
-constexpr int kDeltaMaxSlots = 64;
 constexpr int kDeltaMaxTokens = 16384;
-constexpr int kDeltaWaves = 8;
-constexpr int kDeltaMB = 2;                // 16-row sub-blocks of a workgroup
-constexpr int kDeltaBM = 16 * kDeltaMB;
-constexpr int kDeltaSortThreads = 128;
-
-// ------------------------------------------------------------------------------------------------ group
-__global__ __launch_bounds__(kDeltaSortThreads) void delta_group_kernel(int32_t* offsets, int32_t* sorted_rows,
-                                                                        const int32_t* indices, int T, int S) {
-  __shared__ int hist[kDeltaMaxSlots * kDeltaSortThreads];   // [slot][thread]
-  __shared__ int part[kDeltaSortThreads];
-  const int tid = threadIdx.x;
-  const int chunk = (T + kDeltaSortThreads - 1) / kDeltaSortThreads;
-  const int c0 = min(tid * chunk, T), c1 = min(c0 + chunk, T);
-  for (int s = 0; s < S; ++s) hist[s * kDeltaSortThreads + tid] = 0;
-  for (int t = c0; t < c1; ++t) {
-    const int id = indices[t];
-    if ((unsigned)id < (unsigned)S) ++hist[id * kDeltaSortThreads + tid];
-  }
-  __syncthreads();
-  // exclusive prefix over the flat [slot][thread] order: thread tid owns entries tid S .. tid S + S - 1
-  int sum = 0;
-  for (int j = 0; j < S; ++j) sum += hist[tid * S + j];
-  part[tid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int i = 0; i < kDeltaSortThreads; ++i) {
-      const int x = part[i];
-      part[i] = run;
-      run += x;
-    }
-  }
-  __syncthreads();
-  int run = part[tid];
-  for (int j = 0; j < S; ++j) {
-    const int x = hist[tid * S + j];
-    hist[tid * S + j] = run;
-    run += x;
-  }
-  if (tid == kDeltaSortThreads - 1) offsets[S] = run;       // rows with an index in [0, S)
-  __syncthreads();
-  if (tid < S) offsets[tid] = hist[tid * kDeltaSortThreads];
-  __syncthreads();
-  for (int t = c0; t < c1; ++t) {
-    const int id = indices[t];
-    if ((unsigned)id < (unsigned)S) sorted_rows[hist[id * kDeltaSortThreads + tid]++] = t;   // < offsets[S] <= T
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ product
-typedef float f32x4_d __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_d __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_d __attribute__((ext_vector_type(8)));
-
-template <typename Tag>
-__device__ __forceinline__ f32x4_d mfma_d(const u32x4& a, const u32x4& b, const f32x4_d& c);
-template <>
-__device__ __forceinline__ f32x4_d mfma_d<bf16_tag>(const u32x4& a, const u32x4& b, const f32x4_d& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_d, a), __builtin_bit_cast(bf16x8_d, b),
-                                                 c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4_d mfma_d<f16_tag>(const u32x4& a, const u32x4& b, const f32x4_d& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_d, a), __builtin_bit_cast(f16x8_d, b),
-                                                c, 0, 0, 0);
-}
 
 // one code byte -> (code_lo - 8) in the low and (code_hi - 8) in the high 16 bits, in the activation dtype, exactly
 template <typename Tag>
@@ -159,69 +81,39 @@ struct DeltaArgs {
 };
 
 template <typename Tag>
-__global__ __launch_bounds__(kDeltaWaves * 64) void delta_mm_kernel(DeltaArgs p) {
+__global__ __launch_bounds__(kStreamWaves * 64) void delta_mm_kernel(DeltaArgs p) {
   typedef Elem<Tag> E_;
-  __shared__ float red[kDeltaWaves][kDeltaMB][16 * 17];
-  __shared__ int s_row[kDeltaBM];
+  __shared__ float red[kStreamWaves][kStreamMB][16 * 17];
+  __shared__ int s_row[kStreamBM];
   __shared__ int s_loc[3];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  // (slot, first row, end of the slot's rows) of row block blockIdx.x, or none
-  if (wave == 0) {
-    const int blk = blockIdx.x;
-    int b = 0, en = 0, nb = 0;
-    if (lane < p.S) {
-      b = min(max(p.offsets[lane], 0), p.T);
-      en = min(max(p.offsets[lane + 1], b), p.T);
-      nb = (en - b + kDeltaBM - 1) / kDeltaBM;
-    }
-    int incl = nb;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    const unsigned long long m = __ballot(lane < p.S && blk < incl);
-    if (m == 0) {
-      if (lane == 0) s_loc[0] = -1;
-    } else if (lane == __ffsll((long long)m) - 1) {         // the first such slot has rows
-      s_loc[0] = lane;
-      s_loc[1] = b + (blk - (incl - nb)) * kDeltaBM;
-      s_loc[2] = en;
-    }
-  }
+  if (wave == 0) find_row_block<kStreamBM>(p.offsets, p.S, p.T, s_loc);
   __syncthreads();
   const int slot = s_loc[0];
   if (slot < 0) return;
   const int row0 = s_loc[1], row_end = s_loc[2];
-  if (tid < kDeltaBM) {
-    int row = -1;
-    if (row0 + tid < row_end) {
-      row = p.sorted_rows[row0 + tid];
-      if ((unsigned)row >= (unsigned)p.T) row = -1;
-    }
-    s_row[tid] = row;
-  }
+  block_rows<kStreamBM>(s_row, p.sorted_rows, row0, row_end, p.T);
   __syncthreads();
   const int r16 = lane & 15, q = lane >> 4;
   const int n0 = blockIdx.y * 16;
   const int64_t n = n0 + r16;                               // N % 16 == 0: in range
   const char* cp = p.codes + (int64_t)slot * p.codes_slot_stride + n * (p.K / 4) + 16 * q;
   const char* mp = p.meta + (int64_t)slot * p.meta_slot_stride + n * (p.K / 8) + 8 * q;
-  const char* xp[kDeltaMB];
-  bool valid[kDeltaMB];
+  const char* xp[kStreamMB];
+  bool valid[kStreamMB];
 #pragma unroll
-  for (int sb = 0; sb < kDeltaMB; ++sb) {
+  for (int sb = 0; sb < kStreamMB; ++sb) {
     const int row = s_row[16 * sb + r16];
     valid[sb] = row >= 0;
     xp[sb] = p.x + ((int64_t)max(row, 0) * p.x_stride + 64 * q) * 2;
   }
   const int chunks = p.K / 64;                              // 64 dense columns each
   const int steps = (chunks + 3) / 4;
-  f32x4_d acc[kDeltaMB];
+  f32x4 acc[kStreamMB];
 #pragma unroll
-  for (int sb = 0; sb < kDeltaMB; ++sb) acc[sb] = f32x4_d{0.f, 0.f, 0.f, 0.f};
+  for (int sb = 0; sb < kStreamMB; ++sb) acc[sb] = f32x4{0.f, 0.f, 0.f, 0.f};
   const u32x4 zero = {0u, 0u, 0u, 0u};
-  for (int ss = wave; ss < steps; ss += kDeltaWaves) {
+  for (int ss = wave; ss < steps; ss += kStreamWaves) {
     const bool live = 4 * ss + q < chunks;                  // this lane's 64 columns lie below K
     u32x4 c = {0x88888888u, 0x88888888u, 0x88888888u, 0x88888888u};     // code 8: the value 0
     u32x2 m = {0x44444444u, 0x44444444u};                               // p0 = 0, p1 = 1
@@ -229,11 +121,11 @@ __global__ __launch_bounds__(kDeltaWaves * 64) void delta_mm_kernel(DeltaArgs p)
       c = ld16(cp + (int64_t)ss * 64);
       m = *(const u32x2*)(mp + (int64_t)ss * 32);
     }
-    u32x4 xf[8][kDeltaMB];
+    u32x4 xf[8][kStreamMB];
 #pragma unroll
     for (int j = 0; j < 8; ++j)
 #pragma unroll
-      for (int sb = 0; sb < kDeltaMB; ++sb)
+      for (int sb = 0; sb < kStreamMB; ++sb)
         xf[j][sb] = (live && valid[sb]) ? ld16(xp[sb] + (int64_t)ss * 512 + 16 * j) : zero;
     const uint32_t cw[4] = {c[0], c[1], c[2], c[3]};
     const uint32_t mw[2] = {m[0], m[1]};
@@ -241,24 +133,20 @@ __global__ __launch_bounds__(kDeltaWaves * 64) void delta_mm_kernel(DeltaArgs p)
     for (int j = 0; j < 8; ++j) {
       const u32x4 a = delta_expand<Tag>(cw[j >> 1] >> (16 * (j & 1)), mw[j >> 2] >> (8 * (j & 3)));
 #pragma unroll
-      for (int sb = 0; sb < kDeltaMB; ++sb) acc[sb] = mfma_d<Tag>(a, xf[j][sb], acc[sb]);
+      for (int sb = 0; sb < kStreamMB; ++sb) acc[sb] = mfma_16x16x32<Tag>(a, xf[j][sb], acc[sb]);
     }
   }
   // acc[sb][r] = partial of (row 16 sb + r16 of the block, delta row n0 + 4 q + r)
-#pragma unroll
-  for (int sb = 0; sb < kDeltaMB; ++sb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wave][sb][(4 * q + r) * 17 + r16] = acc[sb][r];
+  park_tile<kStreamMB>(red, wave, r16, q, acc);
   __syncthreads();
-  for (int idx = tid; idx < kDeltaBM * 16; idx += kDeltaWaves * 64) {
+  for (int idx = tid; idx < kStreamBM * 16; idx += kStreamWaves * 64) {
     const int mrow = idx >> 4, col = idx & 15;
     const int row = s_row[mrow];
     if (row < 0) continue;
-    float s = red[0][mrow >> 4][col * 17 + (mrow & 15)];
-#pragma unroll
-    for (int w = 1; w < kDeltaWaves; ++w) s = __fadd_rn(s, red[w][mrow >> 4][col * 17 + (mrow & 15)]);
-    const float sc = E_::load(p.scales, (int64_t)slot * p.scales_slot_stride + n0 + col);
+    // (y's index is formed ahead of the sum so that the scale and y loads are both in flight during it)
     const int64_t yi = (int64_t)row * p.y_stride + n0 + col;
+    const float s = sum_tile<kStreamMB>(red, mrow >> 4, col, mrow & 15);
+    const float sc = E_::load(p.scales, (int64_t)slot * p.scales_slot_stride + n0 + col);
     E_::store(p.y, yi, __fadd_rn(E_::load(p.y, yi), __fmul_rn(sc, s)));
   }
 }
@@ -266,7 +154,7 @@ __global__ __launch_bounds__(kDeltaWaves * 64) void delta_mm_kernel(DeltaArgs p)
 }  // namespace sp
 
 static int delta_shape_status(int64_t num_tokens, int num_slots) {
-  if (num_slots == 0 || num_slots > sp::kDeltaMaxSlots || num_tokens > sp::kDeltaMaxTokens) return SP_ERR_UNSUPPORTED;
+  if (num_slots == 0 || num_slots > sp::kMaxGroups || num_tokens > sp::kDeltaMaxTokens) return SP_ERR_UNSUPPORTED;
   return SP_OK;
 }
 
@@ -276,8 +164,7 @@ extern "C" int sp_delta_group(int32_t* slot_offsets, int32_t* sorted_rows, const
   SP_CHECK_ARG(slot_offsets && sorted_rows && indices);
   if (const int st = delta_shape_status(num_tokens, num_slots)) return st;
   // (num_tokens == 0 still launches: slot_offsets has to read all zero for whoever looks at it)
-  sp::delta_group_kernel<<<1, sp::kDeltaSortThreads, 0, (hipStream_t)stream>>>(slot_offsets, sorted_rows, indices,
-                                                                               (int)num_tokens, num_slots);
+  sp::launch_group_sort(slot_offsets, sorted_rows, indices, (int)num_tokens, num_slots, (hipStream_t)stream);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -301,9 +188,8 @@ extern "C" int sp_delta_mm(void* y, const void* x, const void* codes, const void
   sp::DeltaArgs p{(char*)y, (const char*)x, (const char*)codes, (const char*)meta, (const char*)scales, slot_offsets,
                   sorted_rows, T, num_slots, N, K, x_stride, y_stride, codes_slot_stride, meta_slot_stride,
                   scales_slot_stride};
-  const dim3 grid((unsigned)((T + sp::kDeltaBM - 1) / sp::kDeltaBM + num_slots), (unsigned)(N / 16));
-  if (dtype == SP_BF16) sp::delta_mm_kernel<sp::bf16_tag><<<grid, sp::kDeltaWaves * 64, 0, (hipStream_t)stream>>>(p);
-  else sp::delta_mm_kernel<sp::f16_tag><<<grid, sp::kDeltaWaves * 64, 0, (hipStream_t)stream>>>(p);
+  const dim3 grid((unsigned)((T + sp::kStreamBM - 1) / sp::kStreamBM + num_slots), (unsigned)(N / 16));
+  SP_DISPATCH_16BIT(dtype, (sp::delta_mm_kernel<Tag><<<grid, sp::kStreamWaves * 64, 0, (hipStream_t)stream>>>(p)));
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

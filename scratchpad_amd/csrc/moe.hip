@@ -15,46 +15,29 @@
 // Route.  One wave per token: lane e holds logit e (E <= 64), K rounds of a wave-wide arg-max over a total order
 // (not taken, NaN, value, lower index).  The softmax of the K selected values runs in fp64 (exp, sum in k order,
 // divide) and is rounded to fp32 and then to the activation dtype (two roundings, the reference's): K <= 8 exponentials
-// per token are free, and an fp64 host statement reproduces the result bit for bit.  The sort is ONE workgroup:
-// thread i counts the experts of the i-th contiguous chunk of pairs into its own LDS column, a flat prefix over
-// [expert][thread] gives every (expert, thread) its first slot, and the thread writes its chunk in order.  No atomic:
-// the order is a function of the ids alone.  T <= 16384 (sp_moe_max_tokens): above it the single workgroup's chunks
-// grow past what a prefill chunk needs, and the entry refuses.
+// per token are free, and an fp64 host statement reproduces the result bit for bit.  The sort is the shared one
+// (group_sort.hip).  T <= 16384 (sp_moe_max_tokens): above it the single workgroup's chunks grow past what a prefill
+// chunk needs, and the entry refuses.
 //
-// The two GEMMs are one kernel (moe_gemm_kernel), the weight-streaming form of gemm_skinny.hip made grouped:
-//   * a workgroup (8 waves) owns kMoeBM = 32 consecutive sorted positions of ONE expert x 16 rows of that expert's
-//     weight (gate_up: 8 gate rows and the 8 matching up rows, as epilogue 1 of the skinny kernel);
-//   * grid.x = ceil(T K / BM) + E row blocks, an upper bound computed from (T, K, E); wave 0 finds the block's
-//     (expert, first row) from expert_offsets with one wave prefix sum and the workgroup exits if there is none, so
-//     an expert without rows costs no weight traffic;
-//   * the 8 waves take the k-steps round-robin; per k-step a lane loads 16 B of W (the MFMA A operand) once and 16 B
-//     of each of the two 16-row sub-blocks of activations (B operands, gathered through sorted_pos for gate_up, read
-//     directly for down): one W fragment feeds 2 v_mfma_f32_16x16x32.  8 k-steps of loads are in flight per wave.
-//     No LDS on the way in: at decode the product is a stream of the selected experts' weights (HBM-bound), the
-//     activations of a block (<= 32 x K) come out of L2;
-//   * the waves' partial tiles are summed through LDS in wave order, rounded once, and the epilogue is applied.
+// The two GEMMs are one kernel (moe_gemm_kernel), the grouped form of the weight-streaming core of stream_gemm.h with
+// group = expert (geometry, block search, batch invariance and the safety rules are stated there).  What is its own:
+//   * a workgroup owns 32 consecutive sorted positions of ONE expert x 16 rows of that expert's weight (gate_up: 8
+//     gate rows and the 8 matching up rows, as epilogue 1 of the skinny kernel); one W fragment feeds 2 MFMAs;
+//   * the activations are gathered through sorted_pos for gate_up and read directly for down;
+//   * the epilogues: SiLU-mul, and (down) the routing weight times the rounded sum, scattered to the pair's row.
 // Why BM = 32 and not more: at decode an expert has a handful of rows and a second sub-block costs one idle MFMA per
 // k-step, far below the weight stream; at a prefill chunk the row blocks of one expert re-read its weights out of L2 /
 // the Infinity Cache.  A compute-bound LDS-tiled form for long prefills is left for a later change.
 //
 // BATCH INVARIANCE: the bits of an output row depend on that row's input, its expert's weights and (for down) its
-// routing weight only.  The k-steps of a wave, their order and the order over the waves are functions of the reduction
-// length alone; a row's position inside its block only selects the lane column of the MFMA.
-//
-// Safety: every id is checked against [0, E) and every sorted position / pair index against [0, T K) before an
-// address is formed from it; rows past an expert's end are never loaded or stored; offsets are 64-bit.
-#include "sp_common.h"
+// routing weight only (stream_gemm.h).
+#include "stream_gemm.h"
 
 namespace sp {
 
-constexpr int kMoeMaxExperts = 64;
 constexpr int kMoeMaxTopK = 8;
 constexpr int kMoeMaxTokens = 16384;
-constexpr int kMoeWaves = 8;
-constexpr int kMoeMB = 2;                  // 16-row sub-blocks of a workgroup
-constexpr int kMoeBM = 16 * kMoeMB;
 constexpr int kMoeUnroll = 8;
-constexpr int kSortThreads = 128;
 
 // ------------------------------------------------------------------------------------------------ route
 // is candidate a (index, value, is-NaN) ahead of b?  An index >= 64 marks a lane that cannot be chosen.
@@ -107,68 +90,7 @@ __global__ __launch_bounds__(256) void moe_topk_kernel(int32_t* ids, float* wts,
   }
 }
 
-// stable counting sort of the N = T K pairs by expert, one workgroup
-__global__ __launch_bounds__(kSortThreads) void moe_sort_kernel(int32_t* offsets, int32_t* sorted_pos,
-                                                                const int32_t* ids, int N, int E) {
-  __shared__ int hist[kMoeMaxExperts * kSortThreads];     // [expert][thread]
-  __shared__ int part[kSortThreads];
-  const int tid = threadIdx.x;
-  const int chunk = (N + kSortThreads - 1) / kSortThreads;
-  const int c0 = min(tid * chunk, N), c1 = min(c0 + chunk, N);
-  for (int e = 0; e < E; ++e) hist[e * kSortThreads + tid] = 0;
-  for (int p = c0; p < c1; ++p) {
-    const int id = ids[p];
-    if ((unsigned)id < (unsigned)E) ++hist[id * kSortThreads + tid];
-  }
-  __syncthreads();
-  // exclusive prefix over the flat [expert][thread] order: thread tid owns entries tid E .. tid E + E - 1
-  int s = 0;
-  for (int j = 0; j < E; ++j) s += hist[tid * E + j];
-  part[tid] = s;
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int i = 0; i < kSortThreads; ++i) {
-      const int x = part[i];
-      part[i] = run;
-      run += x;
-    }
-  }
-  __syncthreads();
-  int run = part[tid];
-  for (int j = 0; j < E; ++j) {
-    const int x = hist[tid * E + j];
-    hist[tid * E + j] = run;
-    run += x;
-  }
-  if (tid == kSortThreads - 1) offsets[E] = run;          // pairs with an id in [0, E)
-  __syncthreads();
-  if (tid < E) offsets[tid] = hist[tid * kSortThreads];
-  __syncthreads();
-  for (int p = c0; p < c1; ++p) {
-    const int id = ids[p];
-    if ((unsigned)id < (unsigned)E) sorted_pos[hist[id * kSortThreads + tid]++] = p;   // < offsets[E] <= N
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ grouped GEMM
-typedef float f32x4_m __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_m __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_m __attribute__((ext_vector_type(8)));
-
-template <typename Tag>
-__device__ __forceinline__ f32x4_m mfma_m(const u32x4& a, const u32x4& b, const f32x4_m& c);
-template <>
-__device__ __forceinline__ f32x4_m mfma_m<bf16_tag>(const u32x4& a, const u32x4& b, const f32x4_m& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_m, a), __builtin_bit_cast(bf16x8_m, b),
-                                                 c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4_m mfma_m<f16_tag>(const u32x4& a, const u32x4& b, const f32x4_m& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_m, a), __builtin_bit_cast(f16x8_m, b),
-                                                c, 0, 0, 0);
-}
-
 struct MoeGemmArgs {
   const char* a;                  // GATE_UP: x [T, K]; down: h [T topk, K] by sorted position
   const char* w;                  // [E, rows, K], rows = 2 N (gate | up) resp. N
@@ -181,120 +103,56 @@ struct MoeGemmArgs {
 };
 
 template <typename Tag, bool GATE_UP>
-__global__ __launch_bounds__(kMoeWaves * 64) void moe_gemm_kernel(MoeGemmArgs p) {
+__global__ __launch_bounds__(kStreamWaves * 64) void moe_gemm_kernel(MoeGemmArgs p) {
   typedef Elem<Tag> E_;
-  __shared__ float red[kMoeWaves][kMoeMB][16 * 17];
-  __shared__ int s_pair[kMoeBM];
-  __shared__ float s_scale[kMoeBM];
+  __shared__ float red[kStreamWaves][kStreamMB][16 * 17];
+  __shared__ int s_pair[kStreamBM];
+  __shared__ float s_scale[kStreamBM];
   __shared__ int s_loc[3];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  // (expert, first row, end of the expert's rows) of row block blockIdx.x, or none
-  if (wave == 0) {
-    const int blk = blockIdx.x;
-    int b = 0, en = 0, nb = 0;
-    if (lane < p.E) {
-      b = min(max(p.offsets[lane], 0), p.NP);
-      en = min(max(p.offsets[lane + 1], b), p.NP);
-      nb = (en - b + kMoeBM - 1) / kMoeBM;
-    }
-    int incl = nb;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
-    const unsigned long long m = __ballot(lane < p.E && blk < incl);
-    if (m == 0) {
-      if (lane == 0) s_loc[0] = -1;
-    } else if (lane == __ffsll((long long)m) - 1) {       // the first such expert has rows
-      s_loc[0] = lane;
-      s_loc[1] = b + (blk - (incl - nb)) * kMoeBM;
-      s_loc[2] = en;
-    }
-  }
+  if (wave == 0) find_row_block<kStreamBM>(p.offsets, p.E, p.NP, s_loc);
   __syncthreads();
   const int e = s_loc[0];
   if (e < 0) return;
   const int row0 = s_loc[1], row_end = s_loc[2];
-  if (tid < kMoeBM) {
-    int pair = -1;
-    float sc = 0.f;
-    if (row0 + tid < row_end) {
-      pair = p.sorted_pos[row0 + tid];
-      if ((unsigned)pair >= (unsigned)p.NP) pair = -1;
-      else if (!GATE_UP) sc = p.topk_w[pair];
-    }
-    s_pair[tid] = pair;
-    s_scale[tid] = sc;
-  }
+  const int mine = block_rows<kStreamBM>(s_pair, p.sorted_pos, row0, row_end, p.NP);
+  if (tid < kStreamBM) s_scale[tid] = (!GATE_UP && mine >= 0) ? p.topk_w[mine] : 0.f;
   __syncthreads();
   const int r16 = lane & 15, q = lane >> 4;
   const int n0 = GATE_UP ? blockIdx.y * 8 : blockIdx.y * 16;
   const int n = GATE_UP ? (r16 < 8 ? 0 : p.N) + n0 + (r16 & 7) : n0 + r16;      // N % 8 (16) == 0: in range
-  const char* wp = p.w + ((int64_t)e * p.w_expert_stride + (int64_t)n * p.K + 8 * q) * 2;
-  const char* xp[kMoeMB];
-  bool valid[kMoeMB];
+  const char* const wp[1] = {p.w + ((int64_t)e * p.w_expert_stride + (int64_t)n * p.K + 8 * q) * 2};
+  const char* xp[kStreamMB];
+  int valid[kStreamMB];
 #pragma unroll
-  for (int sb = 0; sb < kMoeMB; ++sb) {
+  for (int sb = 0; sb < kStreamMB; ++sb) {
     const int pair = s_pair[16 * sb + r16];
     valid[sb] = pair >= 0;
     const int64_t arow = GATE_UP ? (int64_t)(max(pair, 0) / p.topk) : (int64_t)row0 + 16 * sb + r16;
     xp[sb] = p.a + (arow * p.a_stride + 8 * q) * 2;
   }
-  const int ksteps = p.K / 32;
-  f32x4_m acc[kMoeMB];
+  f32x4 acc[kStreamMB];
 #pragma unroll
-  for (int sb = 0; sb < kMoeMB; ++sb) acc[sb] = f32x4_m{0.f, 0.f, 0.f, 0.f};
-  const u32x4 zero = {0u, 0u, 0u, 0u};
-  int ks = wave;
-  for (; ks + (kMoeUnroll - 1) * kMoeWaves < ksteps; ks += kMoeUnroll * kMoeWaves) {
-    u32x4 wf[kMoeUnroll], xf[kMoeUnroll][kMoeMB];
-#pragma unroll
-    for (int u = 0; u < kMoeUnroll; ++u) {
-      const int64_t off = (int64_t)(ks + u * kMoeWaves) * 64;
-      wf[u] = ld16(wp + off);
-#pragma unroll
-      for (int sb = 0; sb < kMoeMB; ++sb) xf[u][sb] = valid[sb] ? ld16(xp[sb] + off) : zero;
-    }
-#pragma unroll
-    for (int u = 0; u < kMoeUnroll; ++u)
-#pragma unroll
-      for (int sb = 0; sb < kMoeMB; ++sb) acc[sb] = mfma_m<Tag>(wf[u], xf[u][sb], acc[sb]);
-  }
-  for (; ks < ksteps; ks += kMoeWaves) {
-    const int64_t off = (int64_t)ks * 64;
-    const u32x4 wf = ld16(wp + off);
-#pragma unroll
-    for (int sb = 0; sb < kMoeMB; ++sb) acc[sb] = mfma_m<Tag>(wf, valid[sb] ? ld16(xp[sb] + off) : zero, acc[sb]);
-  }
+  for (int sb = 0; sb < kStreamMB; ++sb) acc[sb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  stream_ksteps<Tag, 1, kStreamMB, kMoeUnroll, false>(acc, wp, xp, valid, wave, p.K / 32);
   // acc[sb][r] = partial of (row 16 sb + r16 of the block, tile column 4 q + r)
-#pragma unroll
-  for (int sb = 0; sb < kMoeMB; ++sb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wave][sb][(4 * q + r) * 17 + r16] = acc[sb][r];
+  park_tile<kStreamMB>(red, wave, r16, q, acc);
   __syncthreads();
   if constexpr (GATE_UP) {
     // tile columns 0-7 are the gate sums, 8-15 the up sums of output columns n0 .. n0 + 7
-    for (int idx = tid; idx < kMoeBM * 8; idx += kMoeWaves * 64) {
+    for (int idx = tid; idx < kStreamBM * 8; idx += kStreamWaves * 64) {
       const int m = idx >> 3, c = idx & 7;
       if (s_pair[m] < 0) continue;
-      float g = 0.f, u = 0.f;
-#pragma unroll
-      for (int w = 0; w < kMoeWaves; ++w) {
-        g += red[w][m >> 4][c * 17 + (m & 15)];
-        u += red[w][m >> 4][(c + 8) * 17 + (m & 15)];
-      }
+      const float g = sum_tile<kStreamMB>(red, m >> 4, c, m & 15), u = sum_tile<kStreamMB>(red, m >> 4, c + 8, m & 15);
       E_::store(p.out, ((int64_t)row0 + m) * p.out_stride + n0 + c,
                 __fmul_rn(E_::round(silu_ref(E_::round(g))), E_::round(u)));
     }
   } else {
-    for (int idx = tid; idx < kMoeBM * 16; idx += kMoeWaves * 64) {
+    for (int idx = tid; idx < kStreamBM * 16; idx += kStreamWaves * 64) {
       const int m = idx >> 4, c = idx & 15;
       const int pair = s_pair[m];
       if (pair < 0) continue;
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < kMoeWaves; ++w) s += red[w][m >> 4][c * 17 + (m & 15)];
+      const float s = sum_tile<kStreamMB>(red, m >> 4, c, m & 15);
       E_::store(p.out, (int64_t)pair * p.out_stride + n0 + c, __fmul_rn(E_::round(s), s_scale[m]));
     }
   }
@@ -335,11 +193,11 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(char* out, const char*
 
 }  // namespace sp
 
-extern "C" int sp_moe_block_rows(void) { return sp::kMoeBM; }
+extern "C" int sp_moe_block_rows(void) { return sp::kStreamBM; }
 extern "C" int sp_moe_max_tokens(void) { return sp::kMoeMaxTokens; }
 
 static int moe_shape_status(int64_t num_tokens, int num_experts, int top_k) {
-  if (num_experts == 0 || num_experts > sp::kMoeMaxExperts || top_k == 0 || top_k > sp::kMoeMaxTopK ||
+  if (num_experts == 0 || num_experts > sp::kMaxGroups || top_k == 0 || top_k > sp::kMoeMaxTopK ||
       top_k > num_experts || num_tokens > sp::kMoeMaxTokens)
     return SP_ERR_UNSUPPORTED;
   return SP_OK;
@@ -359,8 +217,7 @@ extern "C" int sp_moe_route(int32_t* topk_ids, float* topk_weights, int32_t* exp
   SP_DISPATCH_DTYPE(dtype, (sp::moe_topk_kernel<Tag><<<grid, 256, 0, (hipStream_t)stream>>>(
                                topk_ids, topk_weights, router_logits, T, num_experts, top_k, logits_stride)));
   SP_LAUNCH_CHECK();
-  sp::moe_sort_kernel<<<1, sp::kSortThreads, 0, (hipStream_t)stream>>>(expert_offsets, sorted_pos, topk_ids,
-                                                                       T * top_k, num_experts);
+  sp::launch_group_sort(expert_offsets, sorted_pos, topk_ids, T * top_k, num_experts, (hipStream_t)stream);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -388,9 +245,8 @@ extern "C" int sp_moe_gate_up(void* h, const void* x, const void* w13, const int
   const int NP = (int)num_tokens * top_k;
   sp::MoeGemmArgs p{(const char*)x, (const char*)w13, h, expert_offsets, sorted_pos, nullptr, NP, top_k,
                     num_experts, inter, hidden, x_stride, h_stride, w_expert_stride};
-  const dim3 grid((unsigned)((NP + sp::kMoeBM - 1) / sp::kMoeBM + num_experts), (unsigned)(inter / 8));
-  if (dtype == SP_BF16) sp::moe_gemm_kernel<sp::bf16_tag, true><<<grid, sp::kMoeWaves * 64, 0, (hipStream_t)stream>>>(p);
-  else sp::moe_gemm_kernel<sp::f16_tag, true><<<grid, sp::kMoeWaves * 64, 0, (hipStream_t)stream>>>(p);
+  const dim3 grid((unsigned)((NP + sp::kStreamBM - 1) / sp::kStreamBM + num_experts), (unsigned)(inter / 8));
+  SP_DISPATCH_16BIT(dtype, (sp::moe_gemm_kernel<Tag, true><<<grid, sp::kStreamWaves * 64, 0, (hipStream_t)stream>>>(p)));
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -410,9 +266,8 @@ extern "C" int sp_moe_down(void* tmp, const void* h, const void* w2, const float
   const int NP = (int)num_tokens * top_k;
   sp::MoeGemmArgs p{(const char*)h, (const char*)w2, tmp, expert_offsets, sorted_pos, topk_weights, NP, top_k,
                     num_experts, hidden, inter, h_stride, tmp_stride, w_expert_stride};
-  const dim3 grid((unsigned)((NP + sp::kMoeBM - 1) / sp::kMoeBM + num_experts), (unsigned)(hidden / 16));
-  if (dtype == SP_BF16) sp::moe_gemm_kernel<sp::bf16_tag, false><<<grid, sp::kMoeWaves * 64, 0, (hipStream_t)stream>>>(p);
-  else sp::moe_gemm_kernel<sp::f16_tag, false><<<grid, sp::kMoeWaves * 64, 0, (hipStream_t)stream>>>(p);
+  const dim3 grid((unsigned)((NP + sp::kStreamBM - 1) / sp::kStreamBM + num_experts), (unsigned)(hidden / 16));
+  SP_DISPATCH_16BIT(dtype, (sp::moe_gemm_kernel<Tag, false><<<grid, sp::kStreamWaves * 64, 0, (hipStream_t)stream>>>(p)));
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -431,14 +286,9 @@ extern "C" int sp_moe_combine(void* out, const void* tmp, const int32_t* topk_id
   const int64_t col_blocks = ((int64_t)hidden / 8 + 255) / 256;
   SP_CHECK_ARG(col_blocks <= 65535);
   const dim3 grid((unsigned)num_tokens, (unsigned)col_blocks);
-  if (dtype == SP_BF16)
-    sp::moe_combine_kernel<sp::bf16_tag><<<grid, 256, 0, (hipStream_t)stream>>>((char*)out, (const char*)tmp, topk_ids,
-                                                                               top_k, num_experts, hidden, tmp_stride,
-                                                                               out_stride);
-  else
-    sp::moe_combine_kernel<sp::f16_tag><<<grid, 256, 0, (hipStream_t)stream>>>((char*)out, (const char*)tmp, topk_ids,
-                                                                              top_k, num_experts, hidden, tmp_stride,
-                                                                              out_stride);
+  SP_DISPATCH_16BIT(dtype, (sp::moe_combine_kernel<Tag><<<grid, 256, 0, (hipStream_t)stream>>>(
+                               (char*)out, (const char*)tmp, topk_ids, top_k, num_experts, hidden, tmp_stride,
+                               out_stride)));
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

@@ -275,3 +275,11 @@ struct PerDevice {
     else if ((dtype) == SP_BF16) { typedef sp::bf16_tag Tag; __VA_ARGS__; } \
     else return SP_ERR_UNSUPPORTED;                                     \
   } while (0)
+
+// the same for kernels that exist in the two 16-bit dtypes only
+#define SP_DISPATCH_16BIT(dtype, ...)                                   \
+  do {                                                                  \
+    if ((dtype) == SP_BF16) { typedef sp::bf16_tag Tag; __VA_ARGS__; }  \
+    else if ((dtype) == SP_F16) { typedef sp::f16_tag Tag; __VA_ARGS__; } \
+    else return SP_ERR_UNSUPPORTED;                                     \
+  } while (0)
