@@ -7,6 +7,41 @@ from tests import golden
 DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 
 
+def rnd(v: torch.Tensor, dtype) -> torch.Tensor:
+    """fp64 -> fp32 -> dtype, back in fp64: the rounding the kernels apply to an fp32 sum"""
+    return v.to(torch.float32).to(dtype).double()
+
+
+def rerr(v: torch.Tensor, e: torch.Tensor, dtype) -> torch.Tensor:
+    """how far rnd(v) can move when v is known to within e: zero unless v lies within e of a rounding boundary"""
+    r = rnd(v, dtype)
+    return torch.maximum((rnd(v + e, dtype) - r).abs(), (r - rnd(v - e, dtype)).abs())
+
+
+GUARD = 256          # bytes of canary on either side of every Guarded output
+
+
+class Guarded:
+    """outputs carved out of byte buffers pre-filled with 0xA5; check() proves nothing outside them was written"""
+
+    def __init__(self, device="cuda"):
+        self.device = device
+        self.bufs = []
+
+    def alloc(self, shape, dtype):
+        n = 1
+        for s in shape:
+            n *= s
+        nbytes = n * torch.empty((), dtype=dtype).element_size()
+        raw = torch.full((nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=self.device)
+        self.bufs.append((raw, nbytes))
+        return raw[GUARD:GUARD + nbytes].view(dtype).view(*shape)
+
+    def check(self):
+        for raw, nbytes in self.bufs:
+            assert bool((raw[:GUARD] == 0xA5).all()) and bool((raw[GUARD + nbytes:] == 0xA5).all()), "a canary was hit"
+
+
 def T(a, device="cpu", dtype=None):
     t = torch.from_numpy(np.asarray(a))
     if dtype is not None and t.is_floating_point():

@@ -30,18 +30,9 @@ import torch
 from oracle import ops
 from oracle.llama import LlamaShape, OracleKV
 from tests import golden
+from tests.helpers import rerr, rnd  # noqa: F401  (shared with tests/stream_gemm_oracle.py)
 
 U32 = 2.0 ** -24
-
-
-def rnd(v: torch.Tensor, dtype) -> torch.Tensor:
-    """fp64 -> fp32 -> dtype, back in fp64"""
-    return v.to(torch.float32).to(dtype).double()
-
-
-def rerr(v: torch.Tensor, e: torch.Tensor, dtype) -> torch.Tensor:
-    r = rnd(v, dtype)
-    return torch.maximum((rnd(v + e, dtype) - r).abs(), (r - rnd(v - e, dtype)).abs())
 
 
 # --------------------------------------------------------------------------- route

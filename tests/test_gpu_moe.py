@@ -6,30 +6,10 @@ import pytest
 import torch
 
 from tests import moe_oracle
+from tests.helpers import Guarded
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-GUARD = 256          # bytes of canary on either side of every output
-
-
-class Guarded:
-    """outputs carved out of byte buffers pre-filled with 0xA5; check() proves nothing outside them was written"""
-
-    def __init__(self):
-        self.bufs = []
-
-    def alloc(self, shape, dtype):
-        n = 1
-        for s in shape:
-            n *= s
-        nbytes = n * torch.empty((), dtype=dtype).element_size()
-        raw = torch.full((nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=DEV)
-        self.bufs.append((raw, nbytes))
-        return raw[GUARD:GUARD + nbytes].view(dtype).view(*shape)
-
-    def check(self):
-        for raw, nbytes in self.bufs:
-            assert bool((raw[:GUARD] == 0xA5).all()) and bool((raw[GUARD + nbytes:] == 0xA5).all()), "a canary was hit"
 
 
 def sp_dtype(t):

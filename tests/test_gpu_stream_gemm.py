@@ -4,7 +4,11 @@ same sum over the waves, same rounding points), and the two grouping entries are
 
 Reduction lengths: 32 is ONE k-step (seven of the eight waves park zero tiles); 2336 is 73 k-steps (every wave runs one
 unrolled group of 8 and then a one-step tail).  33 rows of one expert are one full 32-row block using both 16-row
-sub-blocks, plus a block of one row."""
+sub-blocks, plus a block of one row.
+
+Agreement is not correctness: a defect in the shared code is shared by both sides of these equalities.  Correctness is
+checked in tests/test_gpu_stream_gemm_oracle.py, which holds each of the three kernels to an fp64 oracle of its own
+(tests/stream_gemm_oracle.py, tests/delta_oracle.py) at every k-step class of the loop."""
 import pytest
 import torch
 
