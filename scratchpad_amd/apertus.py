@@ -8,8 +8,10 @@ checkpoints and state_dicts map 1:1.
 
 The attention block is Qwen3's: per-head RMSNorm of q and k, rotary embedding, KV store - one sp_qk_norm_rotary launch
 on the fused path, the reference's order of separate steps on the other.  SwissAIAttention is qwen3.py's class under
-the reference's constructor; nothing of it is restated here.  The sharded linears, the logits processor, the deferred
-all-reduce protocol under tensor parallelism and the state_dict loader are llama.py's.
+the reference's constructor; nothing of it is restated here.  To llama.py's skeleton this file states only what
+differs: the names of the two layer norms (LlamaDecoderLayer.forward runs the layer protocol, deferred all-reduce
+under tensor parallelism included, over them), the layer class (LlamaModel), and for LlamaForCausalLM no pooler, the
+``get_embedding`` refusal and a stacking table of q_proj / k_proj / v_proj alone - up_proj stands alone.
 
 What is new is the MLP: ``up_proj -> xIELU -> down_proj`` with no gate projection (apertus.py:63-68).  up_proj is
 column-parallel with a single shard, down_proj row-parallel, and the two activation scalars are replicated on every
@@ -20,17 +22,16 @@ library GEMM and sp_xielu runs in place on its result (_native.XIELU_CALLS says 
 Refused with NotImplementedError: ``attention_bias`` / ``bias`` / ``qkv_bias`` / ``mlp_bias``, a
 ``partial_rotary_factor`` other than 1, a ``hidden_act`` other than "xielu".  The reference's ``get_embedding`` /
 pooler branch (apertus.py:336, 353-354) is not built: ``forward(get_embedding=True)`` raises."""
-from typing import Any, Dict, Iterable, Optional, Tuple
+from typing import Any, Dict, Optional
 
 import torch
 from torch import nn
 
 from . import _native
-from .distributed import get_tensor_model_parallel_world_size
 from .forward_info import ForwardBatch
 from .layers import RMSNorm, XIELU
-from .llama import (LlamaForCausalLM, LogitsProcessor, LogitsProcessorOutput, MergedColumnParallelLinear,
-                    ParallelLMHead, RowParallelLinear, VocabParallelEmbedding, norm_after_row_parallel)
+from .llama import (LlamaDecoderLayer, LlamaForCausalLM, LlamaModel, LogitsProcessorOutput,
+                    MergedColumnParallelLinear, RowParallelLinear)
 from .qwen3 import Qwen3Attention
 
 
@@ -69,9 +70,12 @@ class SwissAIAttention(Qwen3Attention):
         self.layer_id = layer_id
 
 
-class SwissAIDecoderLayer(nn.Module):
+class SwissAIDecoderLayer(LlamaDecoderLayer):
+    """apertus.py:179-257; ``forward`` is LlamaDecoderLayer's over this layer's norm names"""
+    norm_names = ("attention_layernorm", "feedforward_layernorm")
+
     def __init__(self, config, layer_id: int = 0, dtype=None):
-        super().__init__()
+        nn.Module.__init__(self)
         self.hidden_size = config.hidden_size
         rope_scaling = getattr(config, "rope_scaling", None)
         if rope_scaling is not None and getattr(config, "original_max_position_embeddings", None):
@@ -92,88 +96,20 @@ class SwissAIDecoderLayer(nn.Module):
         self.attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.feedforward_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
-    def forward(self, positions, hidden_states, forward_batch: ForwardBatch, residual: Optional[torch.Tensor],
-                defer_reduce: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
-        """apertus.py:235-257 with llama.py's deferred all-reduce protocol (LlamaDecoderLayer.forward)."""
-        if residual is None:
-            residual = hidden_states
-            hidden_states = self.attention_layernorm(hidden_states)
-        elif defer_reduce:
-            hidden_states, residual = norm_after_row_parallel(self.attention_layernorm, hidden_states, residual)
-        else:
-            hidden_states, residual = self.attention_layernorm(hidden_states, residual)
-        hidden_states = self.self_attn(positions=positions, hidden_states=hidden_states,
-                                       forward_batch=forward_batch, reduce_output=not defer_reduce)
-        if defer_reduce:
-            hidden_states, residual = norm_after_row_parallel(self.feedforward_layernorm, hidden_states, residual)
-        else:
-            hidden_states, residual = self.feedforward_layernorm(hidden_states, residual)
-        hidden_states = self.mlp(hidden_states, reduce_output=not defer_reduce)
-        return hidden_states, residual
+
+class SwissAIModel(LlamaModel):
+    layer_class = SwissAIDecoderLayer
 
 
-class SwissAIModel(nn.Module):
-    def __init__(self, config, dtype=None):
-        super().__init__()
-        self.config = config
-        self.vocab_size = config.vocab_size
-        self.embed_tokens = VocabParallelEmbedding(config.vocab_size, config.hidden_size, dtype)
-        self.layers = nn.ModuleList(
-            [SwissAIDecoderLayer(config, i, dtype) for i in range(config.num_hidden_layers)])
-        self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
-
-    def forward(self, input_ids, positions, forward_batch: ForwardBatch,
-                input_embeds: torch.Tensor = None) -> torch.Tensor:
-        hidden_states = self.embed_tokens(input_ids) if input_embeds is None else input_embeds
-        residual = None
-        defer = get_tensor_model_parallel_world_size() > 1
-        for layer in self.layers:
-            hidden_states, residual = layer(positions, hidden_states, forward_batch, residual, defer)
-        if defer:
-            hidden_states, _ = norm_after_row_parallel(self.norm, hidden_states, residual)
-        else:
-            hidden_states, _ = self.norm(hidden_states, residual)
-        return hidden_states
-
-
-class SwissAIForCausalLM(nn.Module):
-    def __init__(self, config, dtype=None):
-        super().__init__()
-        self.config = config
-        self.model = SwissAIModel(config, dtype)
-        if getattr(config, "tie_word_embeddings", False):
-            self.lm_head = self.model.embed_tokens
-        else:
-            self.lm_head = ParallelLMHead(config.vocab_size, config.hidden_size, dtype)
-        self.logits_processor = LogitsProcessor(config)
+class SwissAIForCausalLM(LlamaForCausalLM):
+    model_class = SwissAIModel
+    has_pooler = False
+    # apertus.py:406-439: the norm weights and the two activation scalars of every layer load whole
+    stacked_params = {"qkv_proj": ("q_proj", "k_proj", "v_proj")}
 
     @torch.no_grad()
     def forward(self, input_ids, positions, forward_batch: ForwardBatch, input_embeds: torch.Tensor = None,
                 get_embedding: bool = False) -> LogitsProcessorOutput:
         if get_embedding:
             raise NotImplementedError("get_embedding=True (the reference's Pooler branch) is not built")
-        hidden_states = self.model(input_ids, positions, forward_batch, input_embeds)
-        return self.logits_processor(input_ids, hidden_states, self.lm_head, forward_batch)
-
-    # llama.py's loader goes by parameter names and ``shard_from_full`` alone: the norm weights and the two activation
-    # scalars of every layer have no shard_from_full and are copied whole, i.e. replicated on every rank
-    load_full_state_dict = LlamaForCausalLM.load_full_state_dict
-
-    def load_weights(self, weights: Iterable[Tuple[str, torch.Tensor]]) -> None:
-        """HF checkpoint names -> merged parameters (apertus.py:406-439): q_proj / k_proj / v_proj are stacked into
-        qkv_proj and nothing else is - up_proj stands alone.  A tied checkpoint's lm_head is skipped."""
-        tied = getattr(self.config, "tie_word_embeddings", False)
-        staged: Dict[str, Dict[str, torch.Tensor]] = {}
-        full: Dict[str, torch.Tensor] = {}
-        for name, w in weights:
-            if "rotary_emb.inv_freq" in name or (tied and "lm_head.weight" in name):
-                continue
-            for tag in ("q_proj", "k_proj", "v_proj"):
-                if "." + tag + "." in name:
-                    staged.setdefault(name.replace(tag, "qkv_proj"), {})[tag] = w
-                    break
-            else:
-                full[name] = w
-        for name, parts in staged.items():
-            full[name] = torch.cat([parts[t] for t in ("q_proj", "k_proj", "v_proj")], 0)
-        self.load_full_state_dict(full)
+        return super().forward(input_ids, positions, forward_batch, input_embeds)

@@ -9,6 +9,11 @@ RowParallelLinear + all-reduce (1033-1155), VocabParallelEmbedding + all-reduce
 (nn/layers/vocab_parallel_embedding.py:452-472), LogitsProcessor pruning + all-gather
 (nn/layers/logits_processor.py:179-203, 344-376).  GEMMs stay on torch (hipBLASLt/rocBLAS):
 they are outside the path this package re-kernels.
+
+This file is also the decoder skeleton of qwen3.py, apertus.py, llama_moe.py and llama_embedding.py: the attention head
+bookkeeping (LlamaAttention), the layer protocol with its deferred all-reduce (LlamaDecoderLayer.forward), the decoder
+loop (LlamaModel) and the causal-LM shell with both checkpoint loaders (LlamaForCausalLM) exist here once; those files
+subclass them and state only what differs.
 """
 import bisect
 from typing import Any, Dict, Iterable, Optional, Tuple
@@ -456,10 +461,15 @@ class LlamaMLP(nn.Module):
 
 
 class LlamaAttention(nn.Module):
+    """llama.py:69-154.  With ``qk_norm_eps`` it is also the reference's Qwen3Attention (qwen3.py:38-137): a per-head
+    RMSNorm of q and k between qkv_proj and the rotary embedding - on the fused path one launch with the rotation
+    and the KV store (sp_qk_norm_rotary), else the reference's order norm, norm, rotary, store."""
+
     def __init__(self, config, hidden_size: int, num_heads: int, num_kv_heads: int,
                  layer_id: int = 0, rope_theta: float = 10000,
                  rope_scaling: Optional[Dict[str, Any]] = None, rope_is_neox_style: bool = True,
-                 max_position_embeddings: int = 8192, dtype=None):
+                 max_position_embeddings: int = 8192, dtype=None, head_dim: Optional[int] = None,
+                 qk_norm_eps: Optional[float] = None):
         super().__init__()
         self.hidden_size = hidden_size
         tp_size = get_tensor_model_parallel_world_size()
@@ -472,12 +482,18 @@ class LlamaAttention(nn.Module):
         else:
             assert tp_size % self.total_num_kv_heads == 0
         self.num_kv_heads = max(1, self.total_num_kv_heads // tp_size)
-        self.head_dim = getattr(config, "head_dim", None) or self.hidden_size // self.total_num_heads
+        self.head_dim = head_dim or getattr(config, "head_dim", None) or self.hidden_size // self.total_num_heads
         self.q_size = self.num_heads * self.head_dim
         self.kv_size = self.num_kv_heads * self.head_dim
         self.scaling = self.head_dim ** -0.5
         self.rope_theta = rope_theta
         self.max_position_embeddings = max_position_embeddings
+        # [head_dim] weights, replicated on every tensor-parallel rank; registered ahead of qkv_proj, where the
+        # reference's Qwen3Attention has them (the parameter order seeds every random-init model)
+        self.q_norm = self.k_norm = None
+        if qk_norm_eps is not None:
+            self.q_norm = RMSNorm(self.head_dim, eps=qk_norm_eps)
+            self.k_norm = RMSNorm(self.head_dim, eps=qk_norm_eps)
         self.qkv_proj = QKVParallelLinear(hidden_size, self.head_dim, self.total_num_heads,
                                           self.total_num_kv_heads, dtype)
         self.o_proj = RowParallelLinear(self.total_num_heads * self.head_dim, hidden_size, dtype)
@@ -488,17 +504,25 @@ class LlamaAttention(nn.Module):
         self.attn = RadixAttention(self.num_heads, self.head_dim, self.scaling,
                                    num_kv_heads=self.num_kv_heads, layer_id=layer_id)
 
+    def _apply_qk_norm(self, q: torch.Tensor, k: torch.Tensor) -> None:
+        """qwen3.py:114-123, written back into the qkv views the rotary embedding then rotates in place"""
+        q.copy_(self.q_norm(q.reshape(-1, self.head_dim)).view(q.shape))
+        k.copy_(self.k_norm(k.reshape(-1, self.head_dim)).view(k.shape))
+
     def forward(self, positions: torch.Tensor, hidden_states: torch.Tensor,
                 forward_batch: ForwardBatch, reduce_output: bool = True) -> torch.Tensor:
         qkv, _ = self.qkv_proj(hidden_states)
         q, k, v = qkv.split([self.q_size, self.kv_size, self.kv_size], dim=-1)
         backend = forward_batch.attn_backend
         if getattr(backend, "fused_rope_kv_store", False):
-            # one launch: rotate q,k in place AND scatter rotated k + v into the KV pool
-            # (= rotary_emb followed by set_kv_buffer; the backend then skips its own store)
-            backend.rotary_and_store(self.rotary_emb, positions, q, k, v, self.attn, forward_batch)
+            # one launch: (normalise every head of q and k,) rotate them in place AND scatter rotated k + v into the
+            # KV pool (= rotary_emb followed by set_kv_buffer; the backend then skips its own store)
+            backend.rotary_and_store(self.rotary_emb, positions, q, k, v, self.attn, forward_batch,
+                                     q_norm=self.q_norm, k_norm=self.k_norm)
             attn_output = self.attn(q, k, v, forward_batch, save_kv_cache=False)
         else:
+            if self.q_norm is not None:
+                self._apply_qk_norm(q, k)
             q, k = self.rotary_emb(positions, q, k)       # in place on the qkv views
             attn_output = self.attn(q, k, v, forward_batch)
         output, _ = self.o_proj(attn_output, reduce_output)
@@ -506,6 +530,12 @@ class LlamaAttention(nn.Module):
 
 
 class LlamaDecoderLayer(nn.Module):
+    """llama.py:157-224.  ``forward`` is the one statement of the layer protocol for every decoder here: a subclass
+    keeps its own constructor (it calls nn.Module.__init__, not this one) and names its two norms and its
+    feed-forward block, which is called as ``block(x, reduce_output=...)``."""
+    norm_names = ("input_layernorm", "post_attention_layernorm")
+    feed_forward_name = "mlp"
+
     def __init__(self, config, layer_id: int = 0, dtype=None):
         super().__init__()
         self.hidden_size = config.hidden_size
@@ -525,35 +555,40 @@ class LlamaDecoderLayer(nn.Module):
     def forward(self, positions, hidden_states, forward_batch: ForwardBatch,
                 residual: Optional[torch.Tensor], defer_reduce: bool = False
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """llama.py:202-224.  defer_reduce (tensor parallelism only): the all-reduces of o_proj and
-        down_proj are paid inside the norm that follows each of them (norm_after_row_parallel), so the
-        hidden_states that come IN (from the previous layer's down_proj) and go OUT are partial sums."""
+        """llama.py:202-224 (qwen3.py:180-202, apertus.py:235-257, llama_moe.py:170-192).  defer_reduce (tensor
+        parallelism only): the all-reduces of o_proj and down_proj are paid inside the norm that follows each of
+        them (norm_after_row_parallel), so the hidden_states that come IN (from the previous layer's down_proj) and
+        go OUT are partial sums."""
+        attn_norm, ffn_norm = getattr(self, self.norm_names[0]), getattr(self, self.norm_names[1])
         if residual is None:
             residual = hidden_states
-            hidden_states = self.input_layernorm(hidden_states)
+            hidden_states = attn_norm(hidden_states)
         elif defer_reduce:
-            hidden_states, residual = norm_after_row_parallel(self.input_layernorm, hidden_states, residual)
+            hidden_states, residual = norm_after_row_parallel(attn_norm, hidden_states, residual)
         else:
-            hidden_states, residual = self.input_layernorm(hidden_states, residual)
+            hidden_states, residual = attn_norm(hidden_states, residual)
         hidden_states = self.self_attn(positions=positions, hidden_states=hidden_states,
                                        forward_batch=forward_batch, reduce_output=not defer_reduce)
         if defer_reduce:
-            hidden_states, residual = norm_after_row_parallel(self.post_attention_layernorm, hidden_states,
-                                                              residual)
+            hidden_states, residual = norm_after_row_parallel(ffn_norm, hidden_states, residual)
         else:
-            hidden_states, residual = self.post_attention_layernorm(hidden_states, residual)
-        hidden_states = self.mlp(hidden_states, reduce_output=not defer_reduce)
+            hidden_states, residual = ffn_norm(hidden_states, residual)
+        hidden_states = getattr(self, self.feed_forward_name)(hidden_states, reduce_output=not defer_reduce)
         return hidden_states, residual
 
 
 class LlamaModel(nn.Module):
+    """llama.py:227-272: embedding, the layer loop and the final norm of every decoder here; a subclass sets
+    ``layer_class``."""
+    layer_class = LlamaDecoderLayer
+
     def __init__(self, config, dtype=None):
         super().__init__()
         self.config = config
         self.vocab_size = config.vocab_size
         self.embed_tokens = VocabParallelEmbedding(config.vocab_size, config.hidden_size, dtype)
         self.layers = nn.ModuleList(
-            [LlamaDecoderLayer(config, i, dtype) for i in range(config.num_hidden_layers)])
+            [self.layer_class(config, i, dtype) for i in range(config.num_hidden_layers)])
         self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
     def forward(self, input_ids, positions, forward_batch: ForwardBatch,
@@ -595,16 +630,24 @@ def pooled_embedding(decoder: nn.Module, pooler: Pooler, input_ids, positions, f
 
 
 class LlamaForCausalLM(nn.Module):
+    """llama.py:275-311: the causal-LM shell and the checkpoint loaders of every decoder here.  A subclass sets the
+    decoder class, whether it carries the reference's Pooler, and which checkpoint tensors are stacked."""
+    model_class = LlamaModel
+    has_pooler = True
+    # merged parameter -> the HF checkpoint's tensors stacked into it along dim 0, in this order (llama.py:364-405)
+    stacked_params = {"qkv_proj": ("q_proj", "k_proj", "v_proj"), "gate_up_proj": ("gate_proj", "up_proj")}
+
     def __init__(self, config, dtype=None):
         super().__init__()
         self.config = config
-        self.model = LlamaModel(config, dtype)
+        self.model = self.model_class(config, dtype)
         if getattr(config, "tie_word_embeddings", False):
             self.lm_head = self.model.embed_tokens
         else:
             self.lm_head = ParallelLMHead(config.vocab_size, config.hidden_size, dtype)
         self.logits_processor = LogitsProcessor(config)
-        self.pooler = Pooler(pooling_type=PoolingType.LAST, normalize=True)
+        if self.has_pooler:
+            self.pooler = Pooler(pooling_type=PoolingType.LAST, normalize=True)
 
     @torch.no_grad()
     def forward(self, input_ids, positions, forward_batch: ForwardBatch,
@@ -617,7 +660,10 @@ class LlamaForCausalLM(nn.Module):
     # ---- weights ------------------------------------------------------------------------
     def load_full_state_dict(self, full: Dict[str, torch.Tensor]) -> None:
         """Load a tp=1 state_dict in the reference's parameter naming (merged qkv_proj /
-        gate_up_proj), slicing this rank's shard of every tensor-parallel parameter."""
+        gate_up_proj), slicing this rank's shard of every tensor-parallel parameter.  Only the names this model
+        owns are read (a tied checkpoint's lm_head, rotary tables or a dropped head may be present); a parameter
+        whose module has no ``shard_from_full`` - norm weights, activation scalars, a router - is copied whole,
+        i.e. replicated on every rank."""
         own = dict(self.named_parameters())
         mods = dict(self.named_modules())
         for name, param in own.items():
@@ -632,24 +678,16 @@ class LlamaForCausalLM(nn.Module):
 
     def load_weights(self, weights: Iterable[Tuple[str, torch.Tensor]]) -> None:
         """HF checkpoint names (q_proj/k_proj/v_proj, gate_proj/up_proj) -> merged parameters
-        (llama.py:364-405); builds the tp=1 merged dict, then shards."""
-        cfg = self.config
-        D = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-        staged: Dict[str, Dict[str, torch.Tensor]] = {}
+        (llama.py:364-405, ``stacked_params``); builds the tp=1 merged dict, then shards."""
+        staged: Dict[Tuple[str, str], Dict[str, torch.Tensor]] = {}
         full: Dict[str, torch.Tensor] = {}
         for name, w in weights:
-            if "rotary_emb.inv_freq" in name or "rotary_emb.cos_cached" in name or \
-                    "rotary_emb.sin_cached" in name:
-                continue
-            for tag, merged in (("q_proj", "qkv_proj"), ("k_proj", "qkv_proj"), ("v_proj", "qkv_proj"),
-                                ("gate_proj", "gate_up_proj"), ("up_proj", "gate_up_proj")):
+            for merged, tag in ((m, t) for m, tags in self.stacked_params.items() for t in tags):
                 if "." + tag + "." in name:
-                    staged.setdefault(name.replace(tag, merged), {})[tag] = w
+                    staged.setdefault((name.replace(tag, merged), merged), {})[tag] = w
                     break
             else:
                 full[name] = w
-        for name, parts in staged.items():
-            order = ("q_proj", "k_proj", "v_proj") if "qkv_proj" in name else ("gate_proj", "up_proj")
-            full[name] = torch.cat([parts[t] for t in order], 0)
-        del D
+        for (name, merged), parts in staged.items():
+            full[name] = torch.cat([parts[t] for t in self.stacked_params[merged]], 0)
         self.load_full_state_dict(full)

@@ -3,7 +3,9 @@
 Re-hosts nn/models/llama/llama_moe.py (LlamaMLP 32-67, LlamaMoE 70-120, LlamaDecoderLayer 123-192, LlamaModel 195-240,
 LlamaMoEForCausalLM 243-368): the reference's module tree and parameter names - ``moe.gate`` ([E, H], an
 ``nn.Linear``-shaped weight), ``moe.mlp.{i}.gate_up_proj`` / ``moe.mlp.{i}.down_proj`` - so its checkpoints and
-state_dicts map 1:1.  Attention, norms, embedding, LM head, logits processor and the state_dict loader are llama.py's.
+state_dicts map 1:1.  What it adds to llama.py's skeleton is the feed-forward block ``moe`` and the refusals of its
+constructors: the layer protocol (LlamaDecoderLayer.forward), the decoder loop (LlamaModel), the causal-LM shell and
+the loaders (LlamaForCausalLM) are inherited, and attention, norms, embedding and LM head are llama.py's.
 
 The reference's ``LlamaMoE.forward`` loops over the experts with ``torch.where`` and boolean indexing: a host
 synchronisation and a data-dependent shape in every layer, which a HIP-graph replay cannot contain.  Here a 16-bit layer
@@ -20,17 +22,14 @@ capture (``_native.MOE_CALLS`` says which path a step took).
 Refused with NotImplementedError at construction: tensor parallelism (TP > 1), ``grouped_topk``, more than 64 experts
 or more than 8 experts per token.  LoRA toppings on this model and the quantised MoE variants are refused by
 ModelRunner / ModelConfig."""
-from typing import Optional, Tuple
-
 import torch
 from torch import nn
 
-from . import _native
+from . import _native, llama
 from .distributed import get_tensor_model_parallel_world_size
 from .forward_info import ForwardBatch
 from .layers import RMSNorm
-from .llama import (LlamaAttention, LlamaForCausalLM, LogitsProcessor, LogitsProcessorOutput, ParallelLMHead,
-                    VocabParallelEmbedding)
+from .llama import LlamaAttention, LogitsProcessorOutput
 
 
 class _ExpertLinear(nn.Module):
@@ -88,7 +87,8 @@ class LlamaMoE(nn.Module):
         return (a.gate_up_proj.weight.data_ptr() == self.w13[0].data_ptr()
                 and b.down_proj.weight.data_ptr() == self.w2[-1].data_ptr() and self.w13.dtype == a.gate_up_proj.weight.dtype)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, reduce_output: bool = True) -> torch.Tensor:
+        """reduce_output: the layer protocol's keyword; there are no partial sums to leave (TP > 1 is refused)"""
         shape = x.shape
         x = x.reshape(-1, shape[-1])
         if not self._packed():
@@ -101,9 +101,12 @@ class LlamaMoE(nn.Module):
         return out.view(shape)
 
 
-class LlamaDecoderLayer(nn.Module):
+class LlamaDecoderLayer(llama.LlamaDecoderLayer):
+    """llama_moe.py:123-192; ``forward`` is llama.py's LlamaDecoderLayer's over ``moe``"""
+    feed_forward_name = "moe"
+
     def __init__(self, config, layer_id: int = 0, dtype=None):
-        super().__init__()
+        nn.Module.__init__(self)
         self.hidden_size = config.hidden_size
         if getattr(config, "grouped_topk", False):
             raise NotImplementedError("grouped_topk (fused_moe/patch.py) is not built: plain top-k routing only")
@@ -118,60 +121,24 @@ class LlamaDecoderLayer(nn.Module):
         self.input_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
-    def forward(self, positions, hidden_states, forward_batch: ForwardBatch,
-                residual: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """llama_moe.py:170-192"""
-        if residual is None:
-            residual = hidden_states
-            hidden_states = self.input_layernorm(hidden_states)
-        else:
-            hidden_states, residual = self.input_layernorm(hidden_states, residual)
-        hidden_states = self.self_attn(positions=positions, hidden_states=hidden_states, forward_batch=forward_batch)
-        hidden_states, residual = self.post_attention_layernorm(hidden_states, residual)
-        hidden_states = self.moe(hidden_states)
-        return hidden_states, residual
+
+class LlamaModel(llama.LlamaModel):
+    layer_class = LlamaDecoderLayer
 
 
-class LlamaModel(nn.Module):
+class LlamaMoEForCausalLM(llama.LlamaForCausalLM):
+    """llama_moe.py:243-368.  The inherited loaders go by parameter names alone: the per-expert parameters are views
+    of the stacked tensors, so ``moe.mlp.{i}.gate_proj`` / ``up_proj`` are stacked into ``gate_up_proj``
+    (llama_moe.py:317-358) and copied straight into expert i's slot; ``moe.gate.weight`` is copied whole."""
+    model_class = LlamaModel
+    has_pooler = False
+
     def __init__(self, config, dtype=None):
-        super().__init__()
-        self.config = config
-        self.vocab_size = config.vocab_size
-        self.embed_tokens = VocabParallelEmbedding(config.vocab_size, config.hidden_size, dtype)
-        self.layers = nn.ModuleList([LlamaDecoderLayer(config, i, dtype) for i in range(config.num_hidden_layers)])
-        self.norm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
-
-    def forward(self, input_ids, positions, forward_batch: ForwardBatch,
-                input_embeds: torch.Tensor = None) -> torch.Tensor:
-        hidden_states = self.embed_tokens(input_ids) if input_embeds is None else input_embeds
-        residual = None
-        for layer in self.layers:
-            hidden_states, residual = layer(positions, hidden_states, forward_batch, residual)
-        hidden_states, _ = self.norm(hidden_states, residual)
-        return hidden_states
-
-
-class LlamaMoEForCausalLM(nn.Module):
-    def __init__(self, config, dtype=None):
-        super().__init__()
         if get_tensor_model_parallel_world_size() > 1:
             raise NotImplementedError("Llama-MoE under tensor parallelism (TP > 1) is out of scope")
-        self.config = config
-        self.model = LlamaModel(config, dtype)
-        if getattr(config, "tie_word_embeddings", False):
-            self.lm_head = self.model.embed_tokens
-        else:
-            self.lm_head = ParallelLMHead(config.vocab_size, config.hidden_size, dtype)
-        self.logits_processor = LogitsProcessor(config)
+        super().__init__(config, dtype)
 
     @torch.no_grad()
     def forward(self, input_ids, positions, forward_batch: ForwardBatch,
                 input_embeds: torch.Tensor = None) -> LogitsProcessorOutput:
-        hidden_states = self.model(input_ids, positions, forward_batch, input_embeds)
-        return self.logits_processor(input_ids, hidden_states, self.lm_head, forward_batch)
-
-    # llama.py's loaders go by parameter names alone: the per-expert parameters are views of the stacked tensors, so
-    # ``moe.mlp.{i}.gate_proj`` / ``up_proj`` are stacked into ``gate_up_proj`` (llama_moe.py:317-358) and copied
-    # straight into expert i's slot; ``moe.gate.weight`` has no shard_from_full and is copied whole
-    load_full_state_dict = LlamaForCausalLM.load_full_state_dict
-    load_weights = LlamaForCausalLM.load_weights
+        return super().forward(input_ids, positions, forward_batch, input_embeds)

@@ -52,7 +52,29 @@ def _free_port():
     return port
 
 
-def _rank_main(rank, world, port, case, q, custom_ar=False):
+def _family_case(family, case):
+    """(shape, full weights, ModelConfig, the unsharded oracle's forward) of a tiny fixture"""
+    from scratchpad_amd.model_runner import ModelConfig
+    if family != "llama":
+        from tests import apertus_oracle, qwen3_oracle
+        oracle = {"qwen3": qwen3_oracle, "apertus": apertus_oracle}[family]
+        g, pfx, shape, w = oracle.load_case(case)
+        return shape, w, oracle.model_config(shape), oracle.forward
+    from oracle import llama as ollama
+    from tests import smoke_impl
+    g, pfx, shape, w = smoke_impl.load_case(case)
+    scaling = None
+    if shape.rope_scaling is not None:
+        f = shape.rope_scaling
+        scaling = {"rope_type": "llama3", "factor": f[0], "low_freq_factor": f[1], "high_freq_factor": f[2],
+                   "original_max_position_embeddings": int(f[3])}
+    cfg = ModelConfig(shape.hidden, shape.inter, shape.layers, shape.Hq, shape.Hkv, shape.vocab, context_len=60,
+                      rms_norm_eps=shape.rms_eps, rope_theta=shape.rope_theta, rope_scaling=scaling,
+                      max_position_embeddings=shape.max_pos, tie_word_embeddings=shape.tie)
+    return shape, w, cfg, ollama.forward
+
+
+def _rank_main(rank, world, port, case, q, custom_ar=False, family="llama"):
     try:
         os.environ["MASTER_ADDR"] = "127.0.0.1"
         os.environ["MASTER_PORT"] = str(port)
@@ -61,19 +83,10 @@ def _rank_main(rank, world, port, case, q, custom_ar=False):
         from oracle import llama as ollama, ops
         from scratchpad_amd import distributed as d
         from scratchpad_amd.forward_info import ForwardMode, ModelWorkerBatch
-        from scratchpad_amd.model_runner import ModelConfig, ModelRunner, ServerArgs, TpModelWorker
-        from tests import smoke_impl
+        from scratchpad_amd.model_runner import ModelRunner, ServerArgs, TpModelWorker
         d.init_distributed_environment(world, rank, f"tcp://127.0.0.1:{port}", 0, backend="gloo")
         d.initialize_model_parallel(world, backend="gloo", local_rank=0)
-        g, pfx, shape, w = smoke_impl.load_case(case)
-        scaling = None
-        if shape.rope_scaling is not None:
-            f = shape.rope_scaling
-            scaling = {"rope_type": "llama3", "factor": f[0], "low_freq_factor": f[1], "high_freq_factor": f[2],
-                       "original_max_position_embeddings": int(f[3])}
-        cfg = ModelConfig(shape.hidden, shape.inter, shape.layers, shape.Hq, shape.Hkv, shape.vocab, context_len=60,
-                          rms_norm_eps=shape.rms_eps, rope_theta=shape.rope_theta, rope_scaling=scaling,
-                          max_position_embeddings=shape.max_pos, tie_word_embeddings=shape.tie)
+        shape, w, cfg, oracle_forward = _family_case(family, case)
         mr = ModelRunner(cfg, ServerArgs(max_total_tokens=96, max_running_requests=3, disable_cuda_graph=True),
                          tp_rank=rank, tp_size=world, dtype=torch.float32, gpu_id=0, init_weights=False)
         assert mr.token_to_kv_pool.head_num == max(1, shape.Hkv // world), "each rank pools only its KV heads"
@@ -98,7 +111,7 @@ def _rank_main(rank, world, port, case, q, custom_ar=False):
         okv.req_to_token.copy_(table.cpu())
         ext = torch.tensor(lens, dtype=torch.int32)
         pos, start = ops.compute_position(torch.zeros(2, dtype=torch.int32), ext)
-        ref = ollama.forward(shape, w, okv, mode="extend", input_ids=ids, positions=pos, req_pool_indices=req,
+        ref = oracle_forward(shape, w, okv, mode="extend", input_ids=ids, positions=pos, req_pool_indices=req,
                              seq_lens=torch.tensor(lens), out_cache_loc=loc, extend_seq_lens=ext, extend_start_loc=start)
         rel = lambda a, b: float((a.float().cpu() - b).abs().max() / b.abs().max())
         with pytest.raises(RuntimeError, match="gather_full_logits"):
@@ -121,7 +134,7 @@ def _rank_main(rank, world, port, case, q, custom_ar=False):
         out2, _ = worker.forward_batch_generation(batch)
         out2.gather_full_logits()
         okv.req_to_token.copy_(table.cpu())
-        ref2 = ollama.forward(shape, w, okv, mode="decode", input_ids=nxt.cpu(), positions=ops.clamp_position(seq2),
+        ref2 = oracle_forward(shape, w, okv, mode="decode", input_ids=nxt.cpu(), positions=ops.clamp_position(seq2),
                               req_pool_indices=req, seq_lens=seq2, out_cache_loc=loc2)
         assert rel(out2.next_token_logits, ref2) <= 1e-4, ("decode", rank, rel(out2.next_token_logits, ref2))
         torch.distributed.barrier()
@@ -146,6 +159,19 @@ def test_sharded_forward_matches_unsharded_oracle(world, case, custom_ar):
         p.join(timeout=60)
     for rank, err in results:
         assert err is None, f"rank {rank}:\n{err}"
+
+
+def _family_main(rank, world, port, q, case, family):
+    _rank_main(rank, world, port, case, q, family=family)
+
+
+@pytest.mark.parametrize("family", ["qwen3", "apertus"])
+def test_qwen3_and_apertus_run_the_shared_deferred_all_reduce_protocol(family):
+    """Fixture "a" of each (Hq 4 / Hkv 2, the KV heads sharded at world 2; Qwen3 D 128, Apertus inter 96), fp32, the
+    ragged prefill [7, 4] plus one decode step against the unsharded oracle, at the bound of the fp32 Llama cases
+    above.  Their layers inherit LlamaDecoderLayer.forward: two layers, so the second enters with partial sums and
+    pays the previous down_proj's all-reduce in its first norm; two requests make the batch ragged."""
+    _run_ranks(_family_main, 2, ("a", family), timeout=300)
 
 
 def _ar_main(rank, world, port, q, per_device=False):
