@@ -584,6 +584,61 @@ SP_API int sp_moe_down(void* tmp, const void* h, const void* w2, const float* to
 SP_API int sp_moe_combine(void* out, const void* tmp, const int32_t* topk_ids, int64_t num_tokens, int top_k,
                    int num_experts, int hidden, int64_t tmp_stride, int64_t out_stride, int dtype, void* stream);
 
+/* ---- Quantised mixture of experts (additive in ABI 10): the expert half of LlamaQuantisedMoE.forward
+ *      (nn/models/llama/llama_quant_moe.py:204-257) and of the naive variant (llama_naive_quant_moe.py:140-163):
+ *      top_k of num_experts compressed experts on top of a dense base MLP, out = sum_k w_k expert_k(x) + base_mlp(x).
+ *      Routing and the sort are sp_moe_route's, unchanged.  T = num_tokens, K = top_k, E = num_experts, H = hidden,
+ *      I = inter.  `rnd` = round to fp32, then to `dtype`.
+ * The experts are stored in THIS library's packed format, the one stated under "Delta toppings" above (codes / meta /
+ *      scales of a dense [N, red] matrix), stacked over the experts; the reference's qweight / meta / workspace triple
+ *      is in triteia's Marlin tile order and is not converted.  Per projection:
+ *        codes  uint8 [E, N, red / 4]     meta  uint8 [E, N, red / 8]     scales [E, N] in `dtype`
+ *      gate_up: N = 2 I (gate rows first), red = H; down: N = H, red = I.  Expert strides: bytes for codes and meta,
+ *      elements for scales.  An expert of code 8 (any valid meta, any finite scale) contributes exactly 0.
+ * sp_qmoe_gate_up: h[p, n] = rnd( rnd(silu(rnd(sg[n] * G))) * rnd(su[n] * U) ),  G = sum_k x[t, k] q_e[n, k] and U the
+ *      same sum over row I + n, for sorted position p = pair t K + k of expert e (x is gathered through sorted_pos,
+ *      t = pair / K).  ONE fp32 accumulation per sum; the scale is multiplied once, in fp32, behind the sum.
+ *      h [T K, I] is indexed by SORTED POSITION; rows at or past expert_offsets[E] are left untouched.
+ * sp_qmoe_down:    tmp[t K + k, n] = rnd( rnd(s[n] * sum_j h[p, j] q_e[n, j]) * topk_weights[t, k] ).  tmp [T K, H] is
+ *      indexed by PAIR.  topk_weights is fp32 holding values of `dtype`, as sp_moe_route writes it.
+ * sp_qmoe_combine: acc = +0; for the K pairs of token t in the chosen order acc = rnd(acc + tmp[t K + j]); then
+ *      out[t] = rnd(acc + base[t]).  order 0: ascending expert index, ties by k (the naive variant; sp_moe_combine's
+ *      order).  order 1: j = 0 .. K - 1 (the sbmm variant).  out may alias base.  A pair whose id lies outside [0, E)
+ *      is skipped.
+ * Reduction order: sp_delta_mm's by definition (super-steps of 256 columns round-robin over 8 partial sums, 8
+ *      v_mfma_f32_16x16x32 per super-step, folded in order): sp_qmoe_down with K = 1, ascending ids and weights 1.0
+ *      writes the bits sp_delta_mm adds to a zeroed y.
+ * Batch invariance: a token's bits depend on its input, its routing, the packed experts and (H, I) only - not on T,
+ *      its row or how many rows an expert received.
+ * Every offset read from device memory is clamped; every sorted entry and id is range-checked before an address is
+ *      formed from it; byte offsets are 64-bit; every (row, n) has one writer; no atomics and no zero-fill launch.  An
+ *      expert without rows costs no weight traffic.
+ * sp_qmoe_weight_tiles: 16-row weight tiles a workgroup of the two products owns (a build-time figure; it changes no
+ *      element's reduction order).
+ * SP_ERR_UNSUPPORTED: a dtype other than fp16 / bf16; hidden or inter not a positive multiple of 64; E == 0 or > 64;
+ *      K == 0, > 8 or > E; T > 16384; (combine) order not 0 or 1.
+ * SP_ERR_INVALID_ARG before any launch: a NULL pointer, a negative size; a stride below the width it spans (x_stride
+ *      < H, h_stride < I, tmp / base / out strides < H, codes / meta / scales expert strides below N red / 4, N red / 8,
+ *      N); x, h, tmp, base, out or codes not 16-byte aligned, meta not 8-byte aligned, scales not 2-byte aligned;
+ *      x / h / tmp / base / out strides not a multiple of 8, codes expert stride not a multiple of 16, meta expert
+ *      stride not a multiple of 8; more than 65535 grid.y blocks.  T == 0 is SP_OK without a launch.  Like
+ *      sp_gemm_skinny these entries sit on the decode step and do not ask the runtime whether their pointers are
+ *      device memory.                                                                                              */
+SP_API int sp_qmoe_weight_tiles(void);
+SP_API int sp_qmoe_gate_up(void* h, const void* x, const void* codes, const void* meta, const void* scales,
+                    const int32_t* expert_offsets, const int32_t* sorted_pos, int64_t num_tokens, int top_k,
+                    int num_experts, int hidden, int inter, int64_t x_stride, int64_t h_stride,
+                    int64_t codes_expert_stride, int64_t meta_expert_stride, int64_t scales_expert_stride, int dtype,
+                    void* stream);
+SP_API int sp_qmoe_down(void* tmp, const void* h, const void* codes, const void* meta, const void* scales,
+                 const float* topk_weights, const int32_t* expert_offsets, const int32_t* sorted_pos,
+                 int64_t num_tokens, int top_k, int num_experts, int hidden, int inter, int64_t h_stride,
+                 int64_t tmp_stride, int64_t codes_expert_stride, int64_t meta_expert_stride,
+                 int64_t scales_expert_stride, int dtype, void* stream);
+SP_API int sp_qmoe_combine(void* out, const void* tmp, const void* base, const int32_t* topk_ids, int64_t num_tokens,
+                    int top_k, int num_experts, int hidden, int64_t tmp_stride, int64_t base_stride,
+                    int64_t out_stride, int order, int dtype, void* stream);
+
 /* ---- Embedding requests (additive in ABI 10): the final norm of the decoder, Pooler(PoolingType.LAST) and
  *      F.normalize (nn/layers/pooler.py:38-50 behind nn/models/llama/llama.py:268) in one launch, on the num_seqs
  *      rows that matter.  One workgroup per sequence i:

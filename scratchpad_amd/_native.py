@@ -123,6 +123,12 @@ SIGNATURES = {
     "sp_moe_gate_up": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "sp_moe_down": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp]),
     "sp_moe_combine": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _vp]),
+    "sp_qmoe_weight_tiles": (_i32, []),
+    "sp_qmoe_gate_up": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64,
+                               _i64, _i32, _vp]),
+    "sp_qmoe_down": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64,
+                            _i64, _i32, _vp]),
+    "sp_qmoe_combine": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _i32, _vp]),
     "sp_embedding_pool": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _f32, _vp, _i32, _i32, _i64, _i32, _i32, _i32,
                                  _vp]),
 }
@@ -1523,3 +1529,132 @@ def moe_experts_eager(x: torch.Tensor, router_logits: torch.Tensor, w13: torch.T
         out[tok] += linear(act, w2[e]) * wts[tok, k].unsqueeze(-1)
     MOE_CALLS["fallback"] += 1
     return out
+
+
+# --------------------------------------------------------------------------- quantised mixture of experts
+# launches by entry (csrc/quant_moe.hip); the routing in front of them counts in MOE_CALLS["route"].  Tests prove with
+# it that a step ran the kernels.  There is no eager form: fp32 models are refused at construction.
+QMOE_CALLS = {"gate_up": 0, "down": 0, "combine": 0}
+QMOE_ORDER_EXPERT, QMOE_ORDER_RANK = 0, 1       # sp_qmoe_combine's `order`: the naive resp. the sbmm variant
+
+
+def qmoe_weight_tiles() -> int:
+    """16-row weight tiles a workgroup of the two products owns (sp_qmoe_weight_tiles: a build-time figure)"""
+    return int(load().sp_qmoe_weight_tiles())
+
+
+def _qmoe_packed(packed, rows: int, red: int, dtype, what: str):
+    """(codes, meta, scales) stacked over the experts: uint8 [E, rows, red / 4], uint8 [E, rows, red / 8] and [E, rows]
+    in ``dtype``, every expert's rows contiguous"""
+    try:
+        codes, meta, scales = packed
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{what}: packed experts are a (codes, meta, scales) triple") from None
+    _gpu(codes, meta, scales)
+    if codes.dim() != 3 or meta.dim() != 3 or scales.dim() != 2 or codes.dtype != torch.uint8 \
+            or meta.dtype != torch.uint8 or scales.dtype != dtype:
+        raise RuntimeError(f"{what}: codes / meta uint8 [E, N, .] and scales [E, N] in the activation dtype {dtype}")
+    E = codes.shape[0]
+    if red % 8 != 0 or tuple(codes.shape) != (E, rows, red // 4) or tuple(meta.shape) != (E, rows, red // 8) \
+            or tuple(scales.shape) != (E, rows) or codes.stride(2) != 1 or codes.stride(1) != red // 4 \
+            or meta.stride(2) != 1 or meta.stride(1) != red // 8 or scales.stride(1) != 1:
+        raise RuntimeError(f"{what}: codes {tuple(codes.shape)}, meta {tuple(meta.shape)}, scales "
+                           f"{tuple(scales.shape)} do not describe [E, N = {rows}, K = {red}] experts with contiguous "
+                           "rows")
+    return codes, meta, scales
+
+
+def _qmoe_grouping(expert_offsets: torch.Tensor, sorted_pos: torch.Tensor, E: int, NP: int, what: str) -> None:
+    for t, n, name in ((expert_offsets, E + 1, "expert_offsets"), (sorted_pos, NP, "sorted_pos")):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < n or (t.shape[0] > 1 and t.stride(0) != 1):
+            raise RuntimeError(f"{what}: {name} must be a contiguous int32 vector of at least {n} entries")
+
+
+def qmoe_gate_up(x: torch.Tensor, packed13, expert_offsets: torch.Tensor, sorted_pos: torch.Tensor,
+                 top_k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sp_qmoe_gate_up: x [T, H], packed13 = (codes [E, 2 I, H / 4], meta [E, 2 I, H / 8], scales [E, 2 I]) gate rows
+    first -> h [T K, I] by sorted position (rows at or past expert_offsets[E] are left as they were: nothing reads
+    them).  ``out``: the caller's h (tests guard it)."""
+    _gpu(x, expert_offsets, sorted_pos, out)
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise RuntimeError("qmoe_gate_up: x [T, H] with contiguous rows")
+    T, H = x.shape
+    rows = packed13[0].shape[1] if len(packed13) == 3 and packed13[0].dim() == 3 else 0
+    if rows % 2:
+        raise RuntimeError("qmoe_gate_up: the stacked gate | up experts have an even number of rows")
+    codes, meta, scales = _qmoe_packed(packed13, rows, H, x.dtype, "qmoe_gate_up")
+    E, inter, K = codes.shape[0], rows // 2, int(top_k)
+    _qmoe_grouping(expert_offsets, sorted_pos, E, T * K, "qmoe_gate_up")
+    h = torch.empty((T * K, inter), dtype=x.dtype, device=x.device) if out is None else out
+    if h.dim() != 2 or tuple(h.shape) != (T * K, inter) or h.dtype != x.dtype or h.stride(1) != 1:
+        raise RuntimeError(f"qmoe_gate_up: out must be [{T * K}, {inter}] {x.dtype} with contiguous rows")
+    if T == 0:
+        return h
+    _check(load().sp_qmoe_gate_up(h.data_ptr(), x.data_ptr(), codes.data_ptr(), meta.data_ptr(), scales.data_ptr(),
+                                  expert_offsets.data_ptr(), sorted_pos.data_ptr(), T, K, E, H, inter, x.stride(0),
+                                  h.stride(0), codes.stride(0), meta.stride(0), scales.stride(0), _dt(x), _stream()),
+           "sp_qmoe_gate_up")
+    QMOE_CALLS["gate_up"] += 1
+    return h
+
+
+def qmoe_down(h: torch.Tensor, packed2, topk_weights: torch.Tensor, expert_offsets: torch.Tensor,
+              sorted_pos: torch.Tensor, top_k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sp_qmoe_down: h [T K, I] by sorted position, packed2 = (codes [E, H, I / 4], meta [E, H, I / 8], scales [E, H])
+    -> tmp [T K, H] by pair, scaled by the pair's routing weight (fp32 holding values of h's dtype)"""
+    _gpu(h, topk_weights, expert_offsets, sorted_pos, out)
+    K = int(top_k)
+    if h.dim() != 2 or h.stride(1) != 1 or K <= 0 or h.shape[0] % K or topk_weights.dtype != torch.float32 \
+            or not topk_weights.is_contiguous() or topk_weights.numel() != h.shape[0]:
+        raise RuntimeError("qmoe_down: h [T K, I] with contiguous rows and contiguous fp32 weights [T, K]")
+    NP, inter = h.shape
+    H = packed2[0].shape[1] if len(packed2) == 3 and packed2[0].dim() == 3 else 0
+    codes, meta, scales = _qmoe_packed(packed2, H, inter, h.dtype, "qmoe_down")
+    E = codes.shape[0]
+    _qmoe_grouping(expert_offsets, sorted_pos, E, NP, "qmoe_down")
+    tmp = torch.empty((NP, H), dtype=h.dtype, device=h.device) if out is None else out
+    if tmp.dim() != 2 or tuple(tmp.shape) != (NP, H) or tmp.dtype != h.dtype or tmp.stride(1) != 1:
+        raise RuntimeError(f"qmoe_down: out must be [{NP}, {H}] {h.dtype} with contiguous rows")
+    if NP == 0:
+        return tmp
+    _check(load().sp_qmoe_down(tmp.data_ptr(), h.data_ptr(), codes.data_ptr(), meta.data_ptr(), scales.data_ptr(),
+                               topk_weights.data_ptr(), expert_offsets.data_ptr(), sorted_pos.data_ptr(), NP // K, K, E,
+                               H, inter, h.stride(0), tmp.stride(0), codes.stride(0), meta.stride(0), scales.stride(0),
+                               _dt(h), _stream()), "sp_qmoe_down")
+    QMOE_CALLS["down"] += 1
+    return tmp
+
+
+def qmoe_combine(tmp: torch.Tensor, topk_ids: torch.Tensor, num_experts: int, base: torch.Tensor, order: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sp_qmoe_combine: tmp [T K, H] by pair, topk_ids int32 [T, K], base [T, H] -> out [T, H] = the K rows of a token
+    added from zero in ``order`` (QMOE_ORDER_EXPERT / QMOE_ORDER_RANK), then the base row.  ``out`` may be ``base``."""
+    _gpu(tmp, topk_ids, base, out)
+    if tmp.dim() != 2 or tmp.stride(1) != 1 or topk_ids.dtype != torch.int32 or not topk_ids.is_contiguous() \
+            or topk_ids.dim() != 2 or tmp.shape[0] != topk_ids.numel():
+        raise RuntimeError("qmoe_combine: tmp [T K, H] with contiguous rows and contiguous int32 topk_ids [T, K]")
+    T, K = topk_ids.shape
+    H = tmp.shape[1]
+    if base.dim() != 2 or tuple(base.shape) != (T, H) or base.dtype != tmp.dtype or base.stride(1) != 1:
+        raise RuntimeError(f"qmoe_combine: base must be [{T}, {H}] {tmp.dtype} with contiguous rows")
+    if out is None:
+        out = empty_rows(T, H, tmp.dtype, tmp.device)
+    elif out.dim() != 2 or tuple(out.shape) != (T, H) or out.dtype != tmp.dtype or out.stride(1) != 1:
+        raise RuntimeError(f"qmoe_combine: out must be [{T}, {H}] {tmp.dtype} with contiguous rows")
+    if T == 0:
+        return out
+    _check(load().sp_qmoe_combine(out.data_ptr(), tmp.data_ptr(), base.data_ptr(), topk_ids.data_ptr(), T, K,
+                                  int(num_experts), H, tmp.stride(0), base.stride(0), out.stride(0), int(order),
+                                  _dt(tmp), _stream()), "sp_qmoe_combine")
+    QMOE_CALLS["combine"] += 1
+    return out
+
+
+def qmoe_experts(x: torch.Tensor, router_logits: torch.Tensor, packed13, packed2, top_k: int, order: int,
+                 base: torch.Tensor) -> torch.Tensor:
+    """The quantised MoE block behind the router projection and the base MLP: five launches whatever the routing
+    (graph-capturable).  Returns ``base`` with the experts' weighted outputs folded onto it (written in place)."""
+    ids, wts, offsets, pos = moe_route(router_logits, top_k)
+    h = qmoe_gate_up(x, packed13, offsets, pos, top_k)
+    tmp = qmoe_down(h, packed2, wts, offsets, pos, top_k)
+    return qmoe_combine(tmp, ids, packed13[0].shape[0], base, order, out=base)

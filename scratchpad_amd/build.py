@@ -155,8 +155,27 @@ def build_native(force: bool = False, verbose: bool = True) -> str:
     return LIB
 
 
+def build_qmoe_variant(nw: int, verbose: bool = True) -> str:
+    """lib/libscratchpad_hip_qmoe_nw<N>.so: the product with quant_moe.hip's workgroups owning N weight tiles
+    (SP_QMOE_NW), for A/B runs through SP_NATIVE_LIB (tools/bench_quant_moe.py --libs)."""
+    build_native(verbose=verbose)
+    src = os.path.join(CSRC, "quant_moe.hip")
+    obj = os.path.join(OBJ, f"quant_moe_nw{nw}.variant")
+    lib = os.path.join(PKG, "lib", f"libscratchpad_hip_qmoe_nw{nw}.so")
+    objs = [os.path.join(OBJ, os.path.basename(x)[:-4] + ".o") for x in sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+            if os.path.basename(x) != "quant_moe.hip"]
+    for cmd in ([HIPCC] + FLAGS + [f"-DSP_QMOE_NW={nw}", "-c", src, "-o", obj],
+                [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + [obj]):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    return lib
+
+
 if __name__ == "__main__":
-    if "--w64-object" in sys.argv:      # python -m scratchpad_amd.build --w64-object OUT.o [-DFLAG ...]: variant builds
+    if "--qmoe-nw" in sys.argv:         # python -m scratchpad_amd.build --qmoe-nw 2: a variant library for A/B runs
+        print(build_qmoe_variant(int(sys.argv[sys.argv.index("--qmoe-nw") + 1])))
+    elif "--w64-object" in sys.argv:      # python -m scratchpad_amd.build --w64-object OUT.o [-DFLAG ...]: variant builds
         i = sys.argv.index("--w64-object")
         os.makedirs(os.path.dirname(os.path.abspath(sys.argv[i + 1])), exist_ok=True)
         print(compile_w64(os.path.join(CSRC, "extend_w64.hip"), sys.argv[i + 1], extra=sys.argv[i + 2:]))

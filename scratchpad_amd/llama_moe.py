@@ -20,8 +20,8 @@ library product per expert over its gathered rows, added in ascending expert ind
 capture (``_native.MOE_CALLS`` says which path a step took).
 
 Refused with NotImplementedError at construction: tensor parallelism (TP > 1), ``grouped_topk``, more than 64 experts
-or more than 8 experts per token.  LoRA toppings on this model and the quantised MoE variants are refused by
-ModelRunner / ModelConfig."""
+or more than 8 experts per token.  LoRA toppings on this model are refused by ModelRunner.  The quantised MoE
+variants are llama_quant_moe.py's."""
 import torch
 from torch import nn
 

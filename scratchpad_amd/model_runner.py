@@ -22,6 +22,9 @@ from .sampler import Sampler
 from .pool import MHATokenToKVPool, ReqToTokenPool, TokenToKVPoolAllocator
 
 
+QUANT_MOE_ARCHITECTURES = ("llama_quant_moe", "llama_naive_quant_moe")
+
+
 @dataclass
 class ModelConfig:
     """The head/shape math of config/model_config.py:47-99, 155-163 (read-only use)."""
@@ -45,12 +48,18 @@ class ModelConfig:
     # Mllama: the vision tower's config (MllamaVisionConfig fields); None = text side only
     vision_config: Optional[object] = None
     # which decoder load_model builds: "llama" (with cross_attention_layers: Mllama), "qwen3", "apertus",
-    # "llama_moe" or "llama_embedding" (scratchpad_amd/llama_embedding.py: the Llama decoder without an LM head)
+    # "llama_moe", "llama_quant_moe" / "llama_naive_quant_moe" (with expert_layout="sp_delta") or "llama_embedding"
+    # (scratchpad_amd/llama_embedding.py: the Llama decoder without an LM head)
     architecture: str = "llama"
     attention_bias: bool = False        # Qwen3: refused when set (scratchpad_amd/qwen3.py)
     # Llama-MoE (scratchpad_amd/llama_moe.py): experts per layer and experts a token is routed to
     num_experts: Optional[int] = None
     experts_per_token: Optional[int] = None
+    # Llama-Quant-MoE (scratchpad_amd/llama_quant_moe.py): how a checkpoint stores the compressed experts.  None = the
+    # reference's own triteia layout (Marlin tile order), which is refused; "sp_delta" = this library's packed layout
+    # (scratchpad_amd/delta.py), the one that is served
+    expert_layout: Optional[str] = None
+    sbmm_type: Optional[str] = None     # the reference's naive / multilaunch / forloop: one arithmetic here, ignored
     grouped_topk: bool = False          # refused when set: plain top-k routing only
     # serve a generative architecture's checkpoint for embedding requests (server args' is_embedding)
     is_embedding: bool = False
@@ -70,21 +79,29 @@ class ModelConfig:
     def __post_init__(self):
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
-        if self.architecture in ("llama_quant_moe", "llama_naive_quant_moe"):
-            raise NotImplementedError(f"architecture {self.architecture!r}: the quantised MoE models are out of scope "
-                                      "(llama_moe is the one that is built)")
-        if self.architecture not in ("llama", "qwen3", "apertus", "llama_moe", "llama_embedding"):
+        quant_moe = self.architecture in QUANT_MOE_ARCHITECTURES
+        if quant_moe and self.expert_layout is None:
+            raise NotImplementedError(f"architecture {self.architecture!r}: the quantised MoE models are served with "
+                                      "experts in this library's packed layout (expert_layout='sp_delta'); a checkpoint "
+                                      "in the reference's triteia layout (Marlin tile order, expert_layout=None) is not "
+                                      "read or converted")
+        if self.expert_layout not in (None, "sp_delta"):
+            raise ValueError(f"Unsupported expert_layout: {self.expert_layout!r} ('sp_delta')")
+        if self.expert_layout is not None and not quant_moe:
+            raise ValueError(f"expert_layout goes with the quantised MoE architectures, not {self.architecture!r}")
+        if self.architecture not in ("llama", "qwen3", "apertus", "llama_moe", "llama_embedding") and not quant_moe:
             raise ValueError(f"Unsupported architecture: {self.architecture!r} (llama, qwen3, apertus, llama_moe, "
-                             "llama_embedding)")
-        if not self.is_generation and (self.architecture in ("apertus", "llama_moe") or self.cross_attention_layers):
+                             "llama_quant_moe, llama_naive_quant_moe, llama_embedding)")
+        if not self.is_generation and (self.architecture in ("apertus", "llama_moe") or quant_moe
+                                       or self.cross_attention_layers):
             raise NotImplementedError(f"embedding requests on {self.architecture!r}"
                                       f"{' with cross-attention layers' if self.cross_attention_layers else ''}: the "
                                       "pooler branch is built for llama, qwen3 and llama_embedding")
-        if self.architecture == "llama_moe":
+        if self.architecture == "llama_moe" or quant_moe:
             if self.grouped_topk:
                 raise NotImplementedError("grouped_topk is not built: plain top-k routing only")
             if not self.num_experts or not self.experts_per_token:
-                raise ValueError("architecture 'llama_moe' needs num_experts and experts_per_token")
+                raise ValueError(f"architecture {self.architecture!r} needs num_experts and experts_per_token")
             if self.num_experts > 64 or not 0 < self.experts_per_token <= min(self.num_experts, 8):
                 raise NotImplementedError(f"num_experts={self.num_experts}, experts_per_token="
                                           f"{self.experts_per_token}: at most 64 experts and top-8 are built")
@@ -153,6 +170,15 @@ class ModelConfig:
         return cls(4096, 14336, 32, 32, 8, 32000, context_len=context_len, rms_norm_eps=1e-5, rope_theta=1000000.0,
                    max_position_embeddings=max(32768, context_len), architecture="llama_moe", num_experts=8,
                    experts_per_token=2)
+
+    @classmethod
+    def llama3_8b_quant_moe(cls, num_experts: int = 8, experts_per_token: int = 2, context_len: int = 8192):
+        """SYNTHETIC: Llama-3-8B's widths under the reference's Llama-Quant-MoE layout (a dense base MLP plus
+        ``num_experts`` 4-bit 2:4 experts per layer).  No released checkpoint of this shape is known; the preset
+        exists to size and to measure the model."""
+        return cls(4096, 14336, 32, 32, 8, 128256, context_len=context_len,
+                   max_position_embeddings=max(8192, context_len), architecture="llama_quant_moe",
+                   num_experts=num_experts, experts_per_token=experts_per_token, expert_layout="sp_delta")
 
     @classmethod
     def e5_mistral_7b(cls, context_len: int = 4096):
@@ -259,6 +285,17 @@ class ModelRunner:
                     raise NotImplementedError("Llama-MoE under tensor parallelism (TP > 1) is out of scope")
                 from .llama_moe import LlamaMoEForCausalLM
                 self.model = LlamaMoEForCausalLM(self.model_config, dtype=self.dtype).eval()
+            elif self.model_config.architecture in QUANT_MOE_ARCHITECTURES:
+                if self.tp_size > 1:
+                    raise NotImplementedError("Llama-Quant-MoE under tensor parallelism (TP > 1) is out of scope")
+                if self.dtype not in (torch.float16, torch.bfloat16):
+                    raise NotImplementedError(f"Llama-Quant-MoE in {self.dtype}: the expert kernels are fp16 / bf16 "
+                                              "(there is no eager form)")
+                from . import llama_quant_moe
+                cls = (llama_quant_moe.LlamaQuantisedMoEForCausalLM
+                       if self.model_config.architecture == "llama_quant_moe"
+                       else llama_quant_moe.LlamaNaiveQuantisedMoEForCausalLM)
+                self.model = cls(self.model_config, dtype=self.dtype).eval()
             elif self.model_config.architecture == "llama_embedding":
                 from .llama_embedding import LlamaEmbeddingModel
                 self.model = LlamaEmbeddingModel(self.model_config, dtype=self.dtype).eval()
@@ -278,6 +315,8 @@ class ModelRunner:
                     p.data.fill_(0.5)
                 else:
                     p.data.normal_(0.0, 0.02, generator=g)
+            if hasattr(self.model, "init_expert_weights"):      # packed experts are buffers, not parameters
+                self.model.init_expert_weights(g)
 
     def init_toppings(self, adapters):
         """model_runner.py init_toppings: the manager is built after the model (it replaces the target modules)"""
@@ -285,8 +324,8 @@ class ModelRunner:
         if self.tp_size > 1:
             raise NotImplementedError("toppings under tensor parallelism (TP > 1) are out of scope")
         if self.model_config.is_encoder_decoder or self.model_config.architecture != "llama":
-            raise NotImplementedError("toppings are served on Llama only (Mllama, Qwen3, Apertus and Llama-MoE are out "
-                                      "of scope)")
+            raise NotImplementedError("toppings are served on Llama only (Mllama, Qwen3, Apertus, Llama-MoE and "
+                                      "Llama-Quant-MoE are out of scope)")
         max_tokens = max(self.server_args.max_prefill_tokens, self.server_args.cuda_graph_max_bs)
         self.topping_manager = ToppingsManager(self.server_args, self.model, self.model_config, None,
                                                adapters=adapters, device=self.device, dtype=self.dtype,
